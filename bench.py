@@ -1,8 +1,14 @@
 """Benchmark of the MagicDec draft/verify decode loop on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, prefills, warms up, times the K steps and prints the JSON line (`value`, `ms_per_step`).
+`--dump-outputs DIR` also writes what the last timed step left for its caller (DIR/<name>.npy, float64).  `--full`
+adds everything else this file measures: the eager verify-attention pass behind `roofline`, the run with measured
+acceptance, the alpha sweep, the autoregressive baseline behind `speedup_vs_autoregressive`, the PMC traffic passes,
+the other page layout and the CPU baseline.
 
 Workload (BASELINE.json metric "decode tokens/s/node + speedup vs autoregressive, Llama-3.1-8B B=64
 prefix=16K" == configs[2], the tests/SnapKV/longspec_benchmark.py command of the reference's README.md:69):
@@ -19,8 +25,8 @@ when a batch reaches prefix+80 generated tokens the length counters are restored
 Acceptance: random-init weights make measured acceptance meaningless (~0), so `value` uses the fixed-acceptance
 replay of SURVEY.md section 8d -- per-row accept counts drawn from a seeded truncated geometric with alpha=0.8
 (the reference's measured rate, index.html:595-601), E[tokens/iter]=2.952 at gamma=3; every kernel of the
-iteration still runs.  The same line also reports the run with the models' own (random-weight) acceptance and
-the autoregressive baseline (tests/baseline_benchmark.py loop) that defines "speedup".
+iteration still runs.  With --full the same line also reports the run with the models' own (random-weight)
+acceptance and the autoregressive baseline (tests/baseline_benchmark.py loop) that defines "speedup".
 """
 from __future__ import annotations
 
@@ -105,6 +111,13 @@ def parse(argv=None):
                          "Default (round 6): peaked with miss = 0.2, so that the driver's line carries a MEASURED "
                          "acceptance next to the replay that defines `value`; timings are weight-value independent "
                          "(ms_per_step of the two agree to 0.1 %%: profiles/r06_bench_cfg3_peaked_miss_sweep_c7.json)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline (eager verify-attention pass, PMC "
+                         "traffic, other page layout), measured acceptance and its sweep, the alpha sensitivity, the "
+                         "autoregressive baseline (speedup_vs_autoregressive) and the CPU baseline")
+    ap.add_argument("--dump-outputs", type=Path, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step left for the caller of the loop "
+                         "(generated tokens, accept counts, lengths, next draft inputs) as DIR/<name>.npy in float64")
     return ap.parse_args(argv)
 
 
@@ -164,6 +177,22 @@ def truncated_geometric(alpha, gamma, shape, gen, device):
     for j in range(1, gamma + 1):
         a += (u < alpha ** j).long()
     return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per tensor, float64 (every tensor here holds integers below 2^53: exact)."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    host = {name: t.detach().cpu().to(torch.float64).numpy() for name, t in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    for name, a in host.items():
+        np.save(out_dir / f"{name}.npy", a)
 
 
 def self_launch(n, argv=None):
@@ -436,7 +465,8 @@ def run(args, dev):
     draft_step_cap = (128 - BUDGET % 128) if (drf_name is not None and not selfspec and not streaming) else None
     early_restores = [0]
 
-    def run_spec(n_warm, n_steps, forced_table):
+    def run_spec(n_warm, n_steps, forced_table, on_last=None):
+        """`on_last` is called right after the last timed iteration, before a terminal batch is restored."""
         restore()
         nd = False
         since = [0]                                   # draft steps since the counters were last restored
@@ -477,6 +507,8 @@ def run(args, dev):
             nd = guard(nd)
             term, nd = iteration(nd, forced_table[n_warm + i] if forced_table is not None else None)
             stamps.append((time.perf_counter(), bool(term), bool(nd)))   # the iteration ended with a host read
+            if on_last is not None and i == n_steps - 1:
+                on_last()
             if term:
                 restore()
                 nd = False
@@ -543,66 +575,22 @@ def run(args, dev):
 
     gen = torch.Generator(device=dev if on_gpu else "cpu").manual_seed(2024)
     forced = truncated_geometric(args.alpha, G, (args.warmup + args.steps, B), gen, dev)
-    dt_replay, tok_replay = run_spec(args.warmup, args.steps, forced)
+    last = {}
+
+    def snapshot():
+        """What the caller of the loop holds after the last timed iteration (copies: a terminal batch is restored next)."""
+        last.update(generated_tokens=st.output[:, S:].clone(), num_nodes=st.num_nodes.clone(),
+                    accept_nums=st.accept_nums.clone(), bonus=st.bonus.clone(), tokens_buffer=st.tokens_buffer.clone(),
+                    target_cachelens=engine.cachelens.clone())
+        if draft is not None or selfspec:
+            last["draft_cachelens"] = (engine.draft_cachelens if selfspec else draft.cachelens).clone()
+    dump = args.dump_outputs is not None and rank == 0
+    dt_replay, tok_replay = run_spec(args.warmup, args.steps, forced, on_last=snapshot if dump else None)
+    if dump:
+        write_outputs(args.dump_outputs, last)
     if debug_iters:                      # development: is the first timed region slower than a repeat of itself?
         for _ in range(2):
             run_spec(args.warmup, args.steps, forced)
-    if args.graphs:
-        # HIP events cannot be recorded inside a replayed graph: time the verify-attention launches in an eager
-        # pass of the same iterations (same kernels, same shapes, same stream) right after the timed region
-        was = engine._use_graphs            # False if a capture failed and the back-end fell back to eager
-        engine._use_graphs = False
-        run_spec(1, min(args.steps, 8), forced)
-        engine._use_graphs = was
-    attn_ms = timer.mean_ms()
-    n_attn = len(timer.ms)
-    dt_meas, tok_meas = run_spec(min(args.warmup, 2), max(args.steps // 4, 4), None)
-    meas_steps = max(args.steps // 4, 4)
-    # sensitivity of the headline to the assumed acceptance rate: the same loop replayed at other alphas (short runs)
-    sens_steps = max(min(args.steps, 12), 4)
-    sens_raw = {}
-    for al in ((0.5, 0.6, 0.7, 0.8, 0.9) if on_gpu else (args.alpha,)):
-        if abs(al - args.alpha) < 1e-9:
-            sens_raw[al] = (dt_replay / args.steps, tok_replay / args.steps)
-            continue
-        f_al = truncated_geometric(al, G, (2 + sens_steps, B), gen, dev)
-        dt_al, tok_al = run_spec(2, sens_steps, f_al)
-        sens_raw[al] = (dt_al / sens_steps, tok_al / sens_steps)
-
-    # ---- measured acceptance at KNOWN draft quality: with `--weights peaked[...]` the draft's head is
-    # rewritten in place (Engine/utils.repeak_head_: same storage, so the captured graphs stay valid; the draft cache does not
-    # depend on the head) to mispredict a seeded fraction `miss` of the vocabulary, i.e. a draft whose per-step acceptance
-    # rate is ~1 - miss, and the SAME loop runs with the accept kernel's own decisions.  Each point sits beside the
-    # fixed-acceptance replay at alpha = 1 - miss: equal tokens/s there shows the replay is a timing-neutral stand-in.
-    acc_sweep = None
-    # (rank-independent condition: ranks outside the draft sub-group hold no draft model but run the same loops;
-    #  --emulate-tp: partial sums are not reduced, tokens are noise)
-    if on_gpu and emu <= 1 and weights.startswith("peaked") and drf_name is not None and not selfspec:
-        from magicdec_amd.Engine.utils import parse_peaked, repeak_head_
-        miss_cfg = parse_peaked(weights)[2]
-        acc_sweep = {}
-        for miss in (0.4, 0.3, 0.2):
-            if in_draft and draft is not None:
-                repeak_head_(draft.model, miss)
-            dt_m, tok_m = run_spec(2, sens_steps, None)
-            acc_sweep[miss] = (dt_m / sens_steps, tok_m / sens_steps)
-        if in_draft and draft is not None:
-            repeak_head_(draft.model, miss_cfg)
-
-    # ---- autoregressive baseline (tests/baseline_benchmark.py loop: one token per target step)
-    target_step = engine.verify if selfspec else engine.inference
-    restore()
-    nt = first_tok.clone()
-    for _ in range(min(args.warmup, 3)):
-        nt = target_step(nt)
-    restore()
-    base_steps = max(args.steps // 2, 8)
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(base_steps):
-        nt = target_step(nt)
-    barrier()
-    dt_base = time.perf_counter() - t0
 
     def allmax(x):
         if not use_tp:
@@ -610,32 +598,91 @@ def run(args, dev):
         t = torch.tensor([x], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
-    dt_replay, dt_meas, dt_base = allmax(dt_replay), allmax(dt_meas), allmax(dt_base)
-    sens_raw = {al: (allmax(dt), tok) for al, (dt, tok) in sens_raw.items()}
-    if acc_sweep is not None:
-        acc_sweep = {m: (allmax(dt), tok) for m, (dt, tok) in acc_sweep.items()}
-
+    dt_replay = allmax(dt_replay)
     value = tok_replay / dt_replay
-    base_tps = B * base_steps / dt_base
-    cfg = engine.model.config
-    H_loc, KH_loc, D = cfg.n_head, cfg.n_local_heads, cfg.head_dim
-    L_kv = S + 40 + G + 1                                 # mean kv length over a batch's 80 generated tokens
-    kv_elem = 1 if args.kv_dtype == "fp8" else 2
-    attn_bytes = B * L_kv * KH_loc * D * 2 * kv_elem + 2 * B * (G + 1) * H_loc * D * 2
-    achieved = attn_bytes / (attn_ms * 1e-3) / 1e9 if attn_ms > 0 else 0.0
+    if args.full:
+        if args.graphs:
+            # HIP events cannot be recorded inside a replayed graph: time the verify-attention launches in an eager
+            # pass of the same iterations (same kernels, same shapes, same stream) right after the timed region
+            was = engine._use_graphs            # False if a capture failed and the back-end fell back to eager
+            engine._use_graphs = False
+            run_spec(1, min(args.steps, 8), forced)
+            engine._use_graphs = was
+        attn_ms = timer.mean_ms()
+        n_attn = len(timer.ms)
+        dt_meas, tok_meas = run_spec(min(args.warmup, 2), max(args.steps // 4, 4), None)
+        meas_steps = max(args.steps // 4, 4)
+        # sensitivity of the headline to the assumed acceptance rate: the same loop replayed at other alphas (short runs)
+        sens_steps = max(min(args.steps, 12), 4)
+        sens_raw = {}
+        for al in ((0.5, 0.6, 0.7, 0.8, 0.9) if on_gpu else (args.alpha,)):
+            if abs(al - args.alpha) < 1e-9:
+                sens_raw[al] = (dt_replay / args.steps, tok_replay / args.steps)
+                continue
+            f_al = truncated_geometric(al, G, (2 + sens_steps, B), gen, dev)
+            dt_al, tok_al = run_spec(2, sens_steps, f_al)
+            sens_raw[al] = (dt_al / sens_steps, tok_al / sens_steps)
 
-    traffic, traffic_source = None, None
-    want_pmc = args.pmc if getattr(args, "pmc", None) is not None else args.workload.startswith("cfg")
-    if want_pmc and on_gpu and rank == 0:
-        traffic, traffic_source = measure_traffic(B, S + 40 + G + 1, KH_loc, H_loc, D, G + 1, args.kv_dtype == "fp8",
-                                                  kv_layout == "HND")
-    # the same kernel on the OTHER page layout, stand-alone: the line says which layout the headline
-    # ran and what the reference's own layout (NHD) would give
-    other = "NHD" if kv_layout == "HND" else "HND"
-    roofline_other = None
-    if on_gpu and rank == 0 and args.workload.startswith("cfg") and os.environ.get("MAGICDEC_BENCH_LAYOUT_AB", "1") != "0":
-        roofline_other = layout_roofline(engine, timer, B, G + 1, L_kv, H_loc, KH_loc, D, args.kv_dtype == "fp8", other,
-                                         attn_bytes, dev)
+        # ---- measured acceptance at KNOWN draft quality: with `--weights peaked[...]` the draft's head is
+        # rewritten in place (Engine/utils.repeak_head_: same storage, so the captured graphs stay valid; the draft cache does not
+        # depend on the head) to mispredict a seeded fraction `miss` of the vocabulary, i.e. a draft whose per-step acceptance
+        # rate is ~1 - miss, and the SAME loop runs with the accept kernel's own decisions.  Each point sits beside the
+        # fixed-acceptance replay at alpha = 1 - miss: equal tokens/s there shows the replay is a timing-neutral stand-in.
+        acc_sweep = None
+        # (rank-independent condition: ranks outside the draft sub-group hold no draft model but run the same loops;
+        #  --emulate-tp: partial sums are not reduced, tokens are noise)
+        if on_gpu and emu <= 1 and weights.startswith("peaked") and drf_name is not None and not selfspec:
+            from magicdec_amd.Engine.utils import parse_peaked, repeak_head_
+            miss_cfg = parse_peaked(weights)[2]
+            acc_sweep = {}
+            for miss in (0.4, 0.3, 0.2):
+                if in_draft and draft is not None:
+                    repeak_head_(draft.model, miss)
+                dt_m, tok_m = run_spec(2, sens_steps, None)
+                acc_sweep[miss] = (dt_m / sens_steps, tok_m / sens_steps)
+            if in_draft and draft is not None:
+                repeak_head_(draft.model, miss_cfg)
+
+        # ---- autoregressive baseline (tests/baseline_benchmark.py loop: one token per target step)
+        target_step = engine.verify if selfspec else engine.inference
+        restore()
+        nt = first_tok.clone()
+        for _ in range(min(args.warmup, 3)):
+            nt = target_step(nt)
+        restore()
+        base_steps = max(args.steps // 2, 8)
+        barrier()
+        t0 = time.perf_counter()
+        for _ in range(base_steps):
+            nt = target_step(nt)
+        barrier()
+        dt_base = time.perf_counter() - t0
+
+        dt_meas, dt_base = allmax(dt_meas), allmax(dt_base)
+        sens_raw = {al: (allmax(dt), tok) for al, (dt, tok) in sens_raw.items()}
+        if acc_sweep is not None:
+            acc_sweep = {m: (allmax(dt), tok) for m, (dt, tok) in acc_sweep.items()}
+
+        base_tps = B * base_steps / dt_base
+        cfg = engine.model.config
+        H_loc, KH_loc, D = cfg.n_head, cfg.n_local_heads, cfg.head_dim
+        L_kv = S + 40 + G + 1                                 # mean kv length over a batch's 80 generated tokens
+        kv_elem = 1 if args.kv_dtype == "fp8" else 2
+        attn_bytes = B * L_kv * KH_loc * D * 2 * kv_elem + 2 * B * (G + 1) * H_loc * D * 2
+        achieved = attn_bytes / (attn_ms * 1e-3) / 1e9 if attn_ms > 0 else 0.0
+
+        traffic, traffic_source = None, None
+        want_pmc = args.pmc if getattr(args, "pmc", None) is not None else args.workload.startswith("cfg")
+        if want_pmc and on_gpu and rank == 0:
+            traffic, traffic_source = measure_traffic(B, S + 40 + G + 1, KH_loc, H_loc, D, G + 1, args.kv_dtype == "fp8",
+                                                      kv_layout == "HND")
+        # the same kernel on the OTHER page layout, stand-alone: the line says which layout the headline
+        # ran and what the reference's own layout (NHD) would give
+        other = "NHD" if kv_layout == "HND" else "HND"
+        roofline_other = None
+        if on_gpu and rank == 0 and args.workload.startswith("cfg") and os.environ.get("MAGICDEC_BENCH_LAYOUT_AB", "1") != "0":
+            roofline_other = layout_roofline(engine, timer, B, G + 1, L_kv, H_loc, KH_loc, D, args.kv_dtype == "fp8", other,
+                                             attn_bytes, dev)
     # rows the append kernels dropped because a request's last page was full (md_page_overflow_count; the reference would
     # have written them into another request's page): must be 0 -- over every run of this process, not only the headline
     kv_dropped = None
@@ -694,24 +741,29 @@ def run(args, dev):
                    "allreduce_plan": allreduce_plan(engine, draft, B, G, len(rank_group),
                                                     1 if replicate_draft else len(draft_ranks)) if use_tp
                    else None},
-        "speedup_vs_autoregressive": round(value / base_tps, 4),
-        "speedup_condition": speedup_condition({al: tok / dt / base_tps for al, (dt, tok) in sens_raw.items()},
-                                               args.alpha),
-        "alpha_sensitivity": {f"{al:.1f}": {"tokens_per_s": round(tok / dt, 1), "speedup": round(tok / dt / base_tps, 3),
-                                            "tokens_per_iter_per_seq": round(tok / B, 3),
-                                            "ms_per_step": round(dt * 1e3, 3)}
-                              for al, (dt, tok) in sorted(sens_raw.items())},
-        "autoregressive_tokens_per_s": round(base_tps, 2),
-        "autoregressive_ms_per_step": round(dt_base / base_steps * 1e3, 4),
-        "measured_acceptance_run": {"tokens_per_s": round(tok_meas / dt_meas, 2),
-                                    "tokens_per_iter_per_seq": round(tok_meas / meas_steps / B, 3),
-                                    "accepted_drafts_per_drafted": round((tok_meas / meas_steps / B - 1) / G, 4),
-                                    "speedup_vs_autoregressive": round(tok_meas / dt_meas / base_tps, 4),
-                                    "ms_per_step": round(dt_meas / meas_steps * 1e3, 4),
-                                    "weights": weights},
-        "measured_acceptance_sweep": (None if acc_sweep is None else {
-            f"miss={m:.1f}": acceptance_point(dt, tok, B, G, base_tps, sens_raw.get(round(1.0 - m, 1)))
-            for m, (dt, tok) in sorted(acc_sweep.items(), reverse=True)}),
+    }
+    if args.full:
+        line.update({
+            "speedup_vs_autoregressive": round(value / base_tps, 4),
+            "speedup_condition": speedup_condition({al: tok / dt / base_tps for al, (dt, tok) in sens_raw.items()},
+                                                   args.alpha),
+            "alpha_sensitivity": {f"{al:.1f}": {"tokens_per_s": round(tok / dt, 1), "speedup": round(tok / dt / base_tps, 3),
+                                                "tokens_per_iter_per_seq": round(tok / B, 3),
+                                                "ms_per_step": round(dt * 1e3, 3)}
+                                  for al, (dt, tok) in sorted(sens_raw.items())},
+            "autoregressive_tokens_per_s": round(base_tps, 2),
+            "autoregressive_ms_per_step": round(dt_base / base_steps * 1e3, 4),
+            "measured_acceptance_run": {"tokens_per_s": round(tok_meas / dt_meas, 2),
+                                        "tokens_per_iter_per_seq": round(tok_meas / meas_steps / B, 3),
+                                        "accepted_drafts_per_drafted": round((tok_meas / meas_steps / B - 1) / G, 4),
+                                        "speedup_vs_autoregressive": round(tok_meas / dt_meas / base_tps, 4),
+                                        "ms_per_step": round(dt_meas / meas_steps * 1e3, 4),
+                                        "weights": weights},
+            "measured_acceptance_sweep": (None if acc_sweep is None else {
+                f"miss={m:.1f}": acceptance_point(dt, tok, B, G, base_tps, sens_raw.get(round(1.0 - m, 1)))
+                for m, (dt, tok) in sorted(acc_sweep.items(), reverse=True)}),
+        })
+    line.update({
         "prefill_s": round(t_pf, 2), "load_s": round(t_load, 2),
         # what "identical to the reference" means for this path (checked by `pytest -m gpu` and smoke(), not here)
         "parity": {"tokens": "identity with the CPU oracle; zero flips over 16 832 positions at the real layer widths and "
@@ -729,24 +781,25 @@ def run(args, dev):
                                     "threshold go to the lowest index (reference: torch.topk, unspecified among equal "
                                     "scores -- fixture index sets differ by <= 4 of 225 per (request, kv head), all at "
                                     "the threshold score)"},
-        "roofline": {"kernel": f"paged_attn_kernel<{D},{1 if (G + 1) * (H_loc // KH_loc) <= 16 else 2},"
-                               f"{'true' if args.kv_dtype == 'fp8' else 'false'}> (verify attention, md_paged_attn, "
-                               f"{kv_layout} pages)",
-                     "bound": "hbm",
-                     "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                     "bytes_per_launch": attn_bytes, "avg_launch_ms": round(attn_ms, 4), "launches_timed": n_attn,
-                     "timing": "kernel begin/end timestamps of every verify-attention launch of an eager pass "
-                               "(hipExtLaunchKernel start/stop events on the launching stream) = the duration a "
-                               "rocprofv3 kernel trace reports"},
-    }
-    line["roofline"]["kv_cache_layout"] = kv_layout
-    if roofline_other is not None:
-        line["roofline_" + other.lower()] = roofline_other
-    if kv_layout == "NHD":
-        line["roofline_nhd"] = dict(line["roofline"])       # the headline itself ran the reference's layout
-    if rank == 0 and not args.no_cpu_baseline and world == 1 and not selfspec:
-        line["cpu_baseline"] = cpu_baseline(tgt_name, drf_name, S, BUDGET, G, args.alpha)
+    })
+    if args.full:
+        line["roofline"] = {"kernel": f"paged_attn_kernel<{D},{1 if (G + 1) * (H_loc // KH_loc) <= 16 else 2},"
+                                      f"{'true' if args.kv_dtype == 'fp8' else 'false'}> (verify attention, "
+                                      f"md_paged_attn, {kv_layout} pages)",
+                            "bound": "hbm",
+                            "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                            "bytes_per_launch": attn_bytes, "avg_launch_ms": round(attn_ms, 4), "launches_timed": n_attn,
+                            "timing": "kernel begin/end timestamps of every verify-attention launch of an eager pass "
+                                      "(hipExtLaunchKernel start/stop events on the launching stream) = the duration a "
+                                      "rocprofv3 kernel trace reports"}
+        line["roofline"]["kv_cache_layout"] = kv_layout
+        if roofline_other is not None:
+            line["roofline_" + other.lower()] = roofline_other
+        if kv_layout == "NHD":
+            line["roofline_nhd"] = dict(line["roofline"])       # the headline itself ran the reference's layout
+        if rank == 0 and not args.no_cpu_baseline and world == 1 and not selfspec:
+            line["cpu_baseline"] = cpu_baseline(tgt_name, drf_name, S, BUDGET, G, args.alpha)
     if coll_report is not None and rank == 0:
         line["collectives_us"] = coll_report
     if use_tp:

@@ -146,11 +146,12 @@ class KVCache(nn.Module):
     """Paged caches of one layer: `kv_cache` [pages, 2, 128, KH, D] and, for speculation, `draft_cache`."""
 
     def __init__(self, max_num_pages, page_size, n_heads, head_dim, dtype=torch.bfloat16, draft_max_num_pages=0,
-                 kv_len=0, kv_dtype=torch.bfloat16, kv_layout="NHD"):
+                 kv_len=0, kv_dtype=torch.bfloat16, kv_layout="NHD", device=None):
         """kv_dtype=float8_e4m3fn stores `kv_cache` as OCP e4m3fn bytes with static per-kv-head scales
         (`k_scale`, `v_scale`, float32 [KH]; x ~ byte * scale); `draft_cache` is always bf16.
         kv_layout="HND" stores `kv_cache` as [pages, 2, KH, 128, D] (rows of a kv head contiguous: the streaming
-        reads of the verify step become 128-row runs); `draft_cache` is always NHD."""
+        reads of the verify step become 128-row runs); `draft_cache` is always NHD.
+        `device`: where the slabs are allocated (zero-filled there, not on the host and copied)."""
         super().__init__()
         if kv_layout not in ops.KV_LAYOUTS:
             raise ValueError(f"kv_layout must be one of {ops.KV_LAYOUTS}")
@@ -158,7 +159,7 @@ class KVCache(nn.Module):
         if max_num_pages > 0:
             shape = ((max_num_pages, 2, n_heads, page_size, head_dim) if kv_layout == "HND"
                      else (max_num_pages, 2, page_size, n_heads, head_dim))
-            self.register_buffer("kv_cache", torch.zeros(shape, dtype=kv_dtype), persistent=False)
+            self.register_buffer("kv_cache", torch.zeros(shape, dtype=kv_dtype, device=device), persistent=False)
         self.fp8 = kv_dtype == ops.FP8_DTYPE
         if self.fp8:
             self.register_buffer("k_scale", torch.ones(n_heads, dtype=torch.float32), persistent=False)
@@ -166,7 +167,8 @@ class KVCache(nn.Module):
         self.calibrated = False
         if draft_max_num_pages > 0:
             self.register_buffer("draft_cache",
-                                 torch.zeros((draft_max_num_pages, 2, page_size, n_heads, head_dim), dtype=dtype),
+                                 torch.zeros((draft_max_num_pages, 2, page_size, n_heads, head_dim), dtype=dtype,
+                                             device=device),
                                  persistent=False)
         self.kv_len = kv_len
         self.page_size = page_size
@@ -283,7 +285,7 @@ class Transformer(nn.Module):
         for b in self.layers:
             b.attention.kv_cache = KVCache(num_pages, page_size, c.n_local_heads, head_dim, dtype,
                                            draft_num_pages if spec else 0, kv_len=draft_budget,
-                                           kv_dtype=KV_DTYPES[kv_dtype], kv_layout=kv_layout).to(dev)
+                                           kv_dtype=KV_DTYPES[kv_dtype], kv_layout=kv_layout, device=dev).to(dev)
         if max_positions is None:
             max_positions = max(num_pages, draft_num_pages, 1) * page_size + 256
         llama31 = c.high_freq_factor is not None and c.low_freq_factor is not None

@@ -20,7 +20,7 @@ cpu_ops.install()
 import bench
 sys.argv = ["bench.py", "--gpus", os.environ["WORLD_SIZE"], "--steps", "6", "--warmup", "2",
             "--workload", os.environ.get("MD_WORKLOAD", "tiny"),
-            "--no-cpu-baseline", "--draft-tp", os.environ["MD_DRAFT_TP"]]
+            "--no-cpu-baseline", "--draft-tp", os.environ["MD_DRAFT_TP"], "--full"]
 args = bench.parse()
 line = bench.run(args, "cpu")
 if line is not None:
@@ -61,6 +61,57 @@ def test_bench_control_flow_on_cpu(world, draft_tp, workload):
     # decided by rank-independent arithmetic and exists only for longspec + SnapKV draft; these short runs never need it
     early = line["config"]["draft_cache_restores_before_its_page_end"]
     assert early == (0 if workload in ("tiny", "tiny-kh8") else None), (workload, early)
+
+
+PLAIN_WORKER = r'''
+import os, sys, json
+sys.path.insert(0, os.environ["MD_ROOT"])
+from tests import cpu_ops
+cpu_ops.install()
+import bench
+sys.argv = ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "1", "--workload", os.environ["MD_WORKLOAD"],
+            "--dump-outputs", os.environ["MD_DUMP"]]
+json.dump(bench.run(bench.parse(), "cpu"), open(os.environ["MD_OUT"], "w"))
+'''
+
+
+@pytest.mark.parametrize("workload", ["tiny", "tiny-selfspec-snapkv"])
+def test_plain_run_is_the_headline_and_dumps_repeatable_outputs(workload):
+    """Without --full the line carries the headline only (the eager roofline pass, the acceptance runs, the
+    autoregressive baseline and the CPU baseline stay off), --steps is the number of timed steps, and --dump-outputs
+    writes the last timed step's state as float64 .npy files that two runs with the same arguments reproduce."""
+    import numpy as np
+    import bench
+    assert bench.parse([]).full is False and bench.parse([]).dump_outputs is None
+    out = tempfile.mkdtemp(prefix="md_bench_plain_")
+    script = os.path.join(out, "w.py")
+    Path(script).write_text(PLAIN_WORKER)
+    dumps = []
+    for run in range(2):
+        dump = os.path.join(out, f"dump{run}")
+        env = dict(os.environ, MD_ROOT=str(ROOT), MD_OUT=os.path.join(out, f"line{run}.json"), MD_DUMP=dump,
+                   MD_WORKLOAD=workload, OMP_NUM_THREADS="2")
+        for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
+            env.pop(k, None)
+        p = subprocess.run([sys.executable, script], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, cwd=out,
+                           timeout=1200)
+        assert p.returncode == 0, p.stdout.decode()[-3000:]
+        line = json.load(open(os.path.join(out, f"line{run}.json")))
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line, key
+        assert line["steps"] == 5 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+        for key in ("roofline", "speedup_vs_autoregressive", "alpha_sensitivity", "measured_acceptance_run",
+                    "cpu_baseline"):
+            assert key not in line, key
+        files = sorted(os.listdir(dump))
+        assert "generated_tokens.npy" in files and "accept_nums.npy" in files, files
+        arrays = {f: np.load(os.path.join(dump, f)) for f in files}
+        assert all(a.dtype == np.float64 for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys()
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
 
 
 SELF_LAUNCH_WRAPPER = r'''

@@ -26,7 +26,7 @@ def test_plain_bench_gpus_2_on_one_gpu():
     env.update(MAGICDEC_TP_SINGLE_GPU="1", MAGICDEC_BENCH_LAYOUT_AB="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("MAGICDEC_ONESHOT_AR", None)              # let the run choose from its own collectives report
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "cfg3-small", "--steps",
-                        "8", "--warmup", "2", "--no-cpu-baseline", "--no-pmc"], env=env, cwd=ROOT, stdout=subprocess.PIPE,
+                        "8", "--warmup", "2", "--no-cpu-baseline", "--no-pmc", "--full"], env=env, cwd=ROOT, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]

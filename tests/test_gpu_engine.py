@@ -719,7 +719,7 @@ def test_bench_tp_code_path_with_rccl_graphs_one_rank():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE"):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "tiny", "--emulate-tp", "2",
-                        "--no-cpu-baseline", "--steps", "8", "--warmup", "2"], env=env, cwd=root,
+                        "--no-cpu-baseline", "--steps", "8", "--warmup", "2", "--full"], env=env, cwd=root,
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     last = [l for l in p.stdout.splitlines() if l.strip()][-1]

@@ -14,11 +14,11 @@ OUT=$PWD/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${TAG}_bench_cfg3.log 2>&1
+python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/${TAG}_bench_cfg3.log 2>&1
 grep '^{"metric"' $OUT/${TAG}_bench_cfg3.log > $OUT/${TAG}_bench_cfg3.json
 rm -rf /tmp/prof_b /tmp/prof_t
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv rocpd -d /tmp/prof_b -o bench -- \
-    python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-pmc > $OUT/${TAG}_prof_bench.log 2>&1
+    python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-pmc --full > $OUT/${TAG}_prof_bench.log 2>&1
 echo "bench under rocprofv3 rc=$?"
 KS=$(find /tmp/prof_b -name "*kernel_stats.csv" | head -1)
 [ -n "$KS" ] && head -70 "$KS" > $OUT/${TAG}_bench_cfg3_kernel_stats.csv
@@ -26,17 +26,17 @@ DB=$(find /tmp/prof_b -name "*.db" | head -1)
 [ -n "$DB" ] && python tools/iter_breakdown.py $DB $OUT/${TAG}_bench_cfg3_iter_breakdown.csv > /dev/null
 grep '^{"metric"' $OUT/${TAG}_prof_bench.log > $OUT/${TAG}_bench_cfg3_under_rocprofv3.json
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv rocpd -d /tmp/prof_t -o bench -- \
-    python3 bench.py --emulate-tp 8 --steps 20 --warmup 5 --no-cpu-baseline --no-pmc > $OUT/${TAG}_prof_tp8.log 2>&1
+    python3 bench.py --emulate-tp 8 --steps 20 --warmup 5 --no-cpu-baseline --no-pmc --full > $OUT/${TAG}_prof_tp8.log 2>&1
 DB=$(find /tmp/prof_t -name "*.db" | head -1)
 [ -n "$DB" ] && python tools/iter_breakdown.py $DB $OUT/${TAG}_emulated_tp8_iter_breakdown.csv > /dev/null
-python3 bench.py --emulate-tp 8 --steps 20 --warmup 5 --no-cpu-baseline --no-pmc > $OUT/${TAG}_emulated_tp8.log 2>&1
-MAGICDEC_ONESHOT_AR=1 python3 bench.py --emulate-tp 8 --steps 20 --warmup 5 --no-cpu-baseline --no-pmc > $OUT/${TAG}_emulated_tp8_fused_ar.log 2>&1
+python3 bench.py --emulate-tp 8 --steps 20 --warmup 5 --no-cpu-baseline --no-pmc --full > $OUT/${TAG}_emulated_tp8.log 2>&1
+MAGICDEC_ONESHOT_AR=1 python3 bench.py --emulate-tp 8 --steps 20 --warmup 5 --no-cpu-baseline --no-pmc --full > $OUT/${TAG}_emulated_tp8_fused_ar.log 2>&1
 # configs[1] with PEAKED synthetic weights: the fixed-acceptance replay is the headline as before, and the measured-acceptance
 # run beside it now reports what the draft / verify kernels really accept (self-speculation through a StreamingLLM cache)
-python3 bench.py --workload cfg2 --weights peaked --steps 20 --warmup 5 --no-cpu-baseline --no-pmc > $OUT/${TAG}_bench_cfg2.log 2>&1
+python3 bench.py --workload cfg2 --weights peaked --steps 20 --warmup 5 --no-cpu-baseline --no-pmc --full > $OUT/${TAG}_bench_cfg2.log 2>&1
 rm -rf /tmp/prof_c
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv rocpd -d /tmp/prof_c -o bench -- \
-    python3 bench.py --workload cfg2 --weights peaked --steps 20 --warmup 5 --no-cpu-baseline --no-pmc > $OUT/${TAG}_prof_cfg2.log 2>&1
+    python3 bench.py --workload cfg2 --weights peaked --steps 20 --warmup 5 --no-cpu-baseline --no-pmc --full > $OUT/${TAG}_prof_cfg2.log 2>&1
 DB=$(find /tmp/prof_c -name "*.db" | head -1)
 [ -n "$DB" ] && python tools/iter_breakdown.py $DB $OUT/${TAG}_bench_cfg2_iter_breakdown.csv > /dev/null
 # round 6: the GEMM A/Bs behind Engine/gemm_policy.py's new rules and the phase timestamps behind DESIGN.md 3.3's model
