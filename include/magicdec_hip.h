@@ -415,6 +415,74 @@ int md_accept_rollback(int64_t* tokens_buffer, const int64_t* target_tokens, int
                        int64_t* cachelens_update, int32_t* flags, md_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * K11  temperature / top-p sampling and lossless speculative sampling
+ *     reference: Engine/utils.py:68-98 (get_sampling_logits / sample: temperature + top-p filter, multinomial draw;
+ *     cuda_graph_for_target_sample :122-149).  The reference never wires them into a speculative loop; here they
+ *     replace the argmax of every decode loop when a temperature > 0 is asked for (TP = 1 only).
+ * Semantics.  l = a row of bf16 logits, T > 0, invT = fp32(1 / T), m = max(l).
+ *   key(l_v)   order-preserving 16-bit key of the bf16 bit pattern: bits | 0x8000 if the sign is clear, ~bits
+ *              otherwise (a larger key is a larger logit; -0 sorts just below +0).
+ *   w_v        floor(fp32(exp(fp32(l_v - m) * invT)) * 2^40) as uint64 (fixed point: every sum below is an
+ *              integer sum, bit-identical on every run and graph replay);  Z = sum_v w_v.
+ *   top-p      token v is kept iff sum_{u: key_u > key_v} w_u <= top_p * Z (compared in double): the tokens with a
+ *              strictly larger logit carry at most top_p of the mass.  Without ties this is the reference's
+ *              sort / cumsum / shift rule (Engine/utils.py:73-83); a tie group is kept or dropped as a whole.  The
+ *              kept set is {v : key_v >= kstar}; kstar is found by a two-pass 256-bin radix select (high byte,
+ *              then low byte inside the chosen bin); top_p == 1 keeps everything (kstar = 0, no search).
+ *   p~(v)      fp32(w_v) / fp32(Z_kept) on the kept set, 0 elsewhere (Z_kept = sum of the kept w_v).
+ *   draw       Gumbel-max: argmax over kept v of fp32(l_v - m) * invT + G_v, lowest index among equal scores,
+ *              G_v = -log(-log(u_v)) in fp32.
+ *   noise      u_v = (2 (x >> 9) + 1) * 2^-24 (exact in fp32, inside (0, 1)), x = word (v & 3) of
+ *              Philox4x32-10(counter = {v >> 2, b, purpose << 24 | step, iteration}, key = {seed lo, seed hi}),
+ *              b = the request index, `iteration` = counters[0].  A scalar uniform (the accept test) is word 0
+ *              of v = 0.  Keyed by vocab index and request, so a vocab-sharded layout draws the same noise.
+ *   verify     (Leviathan / Chen speculative sampling) for request b, j = 0..gamma-1, d = tokens_buffer[b, j+1],
+ *              p~_j from target row b*(gamma+1)+j, q~_j from draft ring slot [b, j] with its stored stats:
+ *              accept d iff u_j q~_j(d) < p~_j(d) (u_j: purpose ACCEPT, step j).  At the first rejection jr the
+ *              token is a Gumbel-max draw over log max(p~_jr - q~_jr, 0) (purpose RESIDUAL, step jr; if that is 0
+ *              everywhere after rounding: a draw from p~_jr without d); if every draft is accepted, the bonus is a
+ *              draw from p~_gamma (purpose BONUS, step gamma).  Output target_tokens [B, gamma+1] int64: d_j for
+ *              j < jr, the corrected token at jr, -1 after it -- md_accept_rollback, unchanged, then yields the
+ *              accept count and the corrected token (the argument is above the kernel in csrc/sample.hip).
+ * counters: int32 [4] on the device: [0] iteration, [1] draft step j, [2] ticket (0 between launches), [3] unused.
+ *   advance MD_SAMPLE_ADVANCE_STEP: counters[1] += 1 after the launch; MD_SAMPLE_ADVANCE_ITER: counters[0] += 1 and
+ *   counters[1] = 0; md_spec_verify_sample always advances the iteration.  Both entry points read the counters on
+ *   the device, so one captured hipGraph serves every step and every iteration.
+ * md_sample_rows: per request b (B workgroups), ONE row of logits [B*n, row_stride] bf16 is drawn: row
+ *   b*n + row_sel[b]-1 (row_sel may be NULL: the last row; the draft's two-token step) and the token written to
+ *   tokens_out[b, 0..n-1].  Noise step = counters[1] when ring != NULL (draft mode), else 0.  In draft mode the row
+ *   is also copied to ring[b, j, :] ([B, gamma, vocab] bf16) and its stats to ring_stats[b, j] (j = counters[1],
+ *   stored only if j < gamma).
+ * md_spec_verify_sample: stats of the B*(gamma+1) target rows into target_stats (workspace [B*(gamma+1)]), then the
+ *   verify above; advances the iteration counter (and resets the step).
+ * md_philox4x32_10_host: out[i] = Philox4x32-10(ctr[i], {key0, key1}) for n counters of 4 words (host memory). Host.
+ * ---------------------------------------------------------------------- */
+#define MD_SAMPLE_PREFILL 0
+#define MD_SAMPLE_BASELINE 1
+#define MD_SAMPLE_DRAFT 2
+#define MD_SAMPLE_ACCEPT 3
+#define MD_SAMPLE_RESIDUAL 4
+#define MD_SAMPLE_BONUS 5
+#define MD_SAMPLE_ADVANCE_NONE 0
+#define MD_SAMPLE_ADVANCE_STEP 1
+#define MD_SAMPLE_ADVANCE_ITER 2
+typedef struct md_sample_stats {
+    float m;            /* row max */
+    uint32_t kstar;     /* smallest kept key */
+    uint64_t zkept;     /* Z_kept, fixed point 2^40 */
+} md_sample_stats;
+int md_philox4x32_10_host(const uint32_t* ctr_host, int n, uint32_t key0, uint32_t key1, uint32_t* out_host);
+int md_sample_rows(const void* logits, int64_t row_stride, int B, int n, int vocab, float temperature, float top_p,
+                   uint64_t seed, int purpose, const int64_t* row_sel /* [B] or NULL */, int32_t* counters,
+                   int advance, void* ring /* [B,gamma,vocab] bf16 or NULL */,
+                   void* ring_stats /* md_sample_stats [B,gamma] or NULL */, int gamma,
+                   int64_t* tokens_out /* [B,n] */, md_stream_t stream);
+int md_spec_verify_sample(const void* logits, int64_t row_stride, int B, int gamma, int vocab, float temperature,
+                          float top_p, uint64_t seed, const int64_t* tokens_buffer /* [B,gamma+1] */,
+                          const void* ring, const void* ring_stats, void* target_stats /* [B*(gamma+1)] */,
+                          int32_t* counters, int64_t* target_tokens /* [B,gamma+1] */, md_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * C1  the per-layer sum-all-reduce of the tensor-parallel decode path over xGMI peer-mapped buffers
  *     reference: dist.all_reduce at Engine/SnapKV/model.py:334-335,453-454 (and the StreamingLLM twins), NCCL with
  *     PyTorch's intra-node one-/two-shot kernels (README.md:59 ENABLE_INTRA_NODE_COMM=1); the fused form also

@@ -225,6 +225,7 @@ class SnapKVTargetBackend(_BackendBase):
                 is_last = True
             self._t.map_pages(i + 1, n)                       # pre_encode
             self.model.skip_head = i != num_chunks - 1
+            self.model.sample_role = "prefill"
             tokens = self.model.prefill(ids, self.cachelens, self._qo(n), self._t.table(), is_last=is_last,
                                         draft_tab=self._d.table() if (self.is_spec and is_last) else None,
                                         ctx_len=done + n)
@@ -244,6 +245,7 @@ class SnapKVTargetBackend(_BackendBase):
         """Autoregressive step / longspec verification (backend.py:129-159)."""
         n = input_ids.shape[1]
         self.paged_kv_last_page_len += n                      # pre_decode
+        self.model.sample_role = "verify" if n > 1 else "baseline"
         out = self._run_step(("fwd", n), lambda ids: self.model.forward(ids, self.cachelens, self._qo(n),
                                                                           self._t.table()), input_ids)
         self.cachelens += n
@@ -259,6 +261,7 @@ class SnapKVTargetBackend(_BackendBase):
         self.paged_kv_last_page_len += n                      # pre_verify
         self.draft_paged_kv_last_page_len += 1
         self.draft_cachelens += 1
+        self.model.sample_role = "verify"
         out = self._run_step(("verify", n), lambda ids: self.model.verify(ids, self.cachelens, self._qo(n),
                                                                             self._t.table(), self._d.table()),
                              input_ids)
@@ -273,6 +276,7 @@ class SnapKVTargetBackend(_BackendBase):
         """Self-spec draft step over the SnapKV draft cache (backend.py:200-229)."""
         n = input_ids.shape[1]
         self.draft_paged_kv_last_page_len += n                # pre_spec
+        self.model.sample_role = "draft"
         out = self._run_step(("spec", n), lambda ids: self.model.draft_forward(ids, self.draft_cachelens, self._qo(n),
                                                                                  self._d.table()), input_ids)
         self.draft_cachelens += n
@@ -346,6 +350,7 @@ class SnapKVDraftBackend(_BackendBase):
                 is_last = True
             self._t.map_pages(i + 1, n)
             self.model.skip_head = i != num_chunks - 1
+            self.model.sample_role = "prefill"
             tokens = self.model.prefill(ids, self.cachelens, self._qo(n), self._t.table(), is_last=is_last,
                                         draft_tab=self._d.table() if (self.is_compress and is_last) else None,
                                         ctx_len=done + n)
@@ -362,6 +367,7 @@ class SnapKVDraftBackend(_BackendBase):
     def inference(self, input_ids: torch.LongTensor, benchmark=False, cachelen_update=None):
         """One (or, after an all-accept iteration, a two-token) draft step (backend_draft.py:113-173)."""
         n = input_ids.shape[1]
+        self.model.sample_role = "draft"
         if self.is_compress:
             self.draft_paged_kv_last_page_len += n            # pre_decode
             out = self._run_step(("draft", n), lambda ids: self.model.draft_forward(ids, self.cachelens, self._qo(n),
@@ -406,6 +412,7 @@ class _StreamingMixin:
             else:
                 state.map_pages(state.ppr, self.draft_budget % PAGE_SIZE)
             self.model.skip_head = i != num_chunks - 1
+            self.model.sample_role = "prefill"
             tokens = self.model.stream_prefill(ids, ctx, self._qo(n), state.table(), is_last, which, self.batch_size)
             ctx += n
             lens = getattr(self, lens_attr)
@@ -458,6 +465,7 @@ class StreamingDraftBackend(_BackendBase, _StreamingMixin):
     def inference(self, input_ids: torch.LongTensor, benchmark=False, cachelen_update=None):
         """StreamingLLM/backend_draft.py:89-124."""
         n = input_ids.shape[1]
+        self.model.sample_role = "draft"
         self.paged_kv_last_page_len += n
         out = self._run_step(("fwd", n), lambda ids: self.model.forward(ids, self.cachelens, self._qo(n),
                                                                           self._t.table()), input_ids)
@@ -529,6 +537,7 @@ class StreamingSelfSpecBackend(_BackendBase, _StreamingMixin):
             n = ids.shape[1]
             self._t.map_pages(i + 1, n)
             self.model.skip_head = i != num_chunks - 1
+            self.model.sample_role = "prefill"
             tokens = self.model.prefill(ids, self.cachelens, self._qo(n), self._t.table())
             self.cachelens += n
         self.model.skip_head = False
@@ -544,6 +553,7 @@ class StreamingSelfSpecBackend(_BackendBase, _StreamingMixin):
     def verify(self, input_ids: torch.LongTensor, benchmark=False):
         n = input_ids.shape[1]
         self.paged_kv_last_page_len += n
+        self.model.sample_role = "verify"
         out = self._run_step(("verify", n), lambda ids: self.model.verify(ids, self.cachelens, self._qo(n),
                                                                             self._t.table()), input_ids)
         self.cachelens += n
@@ -556,6 +566,7 @@ class StreamingSelfSpecBackend(_BackendBase, _StreamingMixin):
     def speculate(self, input_ids: torch.LongTensor, benchmark=False, cachelen_update=None):
         n = input_ids.shape[1]
         self.draft_paged_kv_last_page_len += n
+        self.model.sample_role = "draft"
         out = self._run_step(("spec", n), lambda ids: self.model.draft_forward(ids, self.draft_cachelens,
                                                                                  self._qo(n), self._d.table()),
                              input_ids)

@@ -135,6 +135,9 @@ def run_captured(backend, key, fn, input_ids):
         ent.names = tuple(names)
         _bind_state(backend, ent)
         ent.static_in = input_ids.clone()
+        # a sampling step advances its noise counters on the device: the warm-up runs below must not
+        smp = getattr(getattr(backend, "model", None), "sampler", None)
+        smp_saved = smp.save() if smp is not None else None
         # warm up on a side stream (hipBLASLt workspaces, lazy module loads, LDS attributes); a step never
         # changes the lengths it reads, and re-running it rewrites the same KV rows with the same values
         s = torch.cuda.Stream()
@@ -164,6 +167,9 @@ def run_captured(backend, key, fn, input_ids):
                 _recover_from_failed_capture(g, home)
                 if invalidated:
                     _CAPTURE_POISONED[0] = f"step {key}: {type(e).__name__}"
+        if smp is not None:
+            smp.restore(smp_saved)
+            smp.captured = err is None
         # Under tensor parallelism every rank captures the same step at the same point of the same program, but a
         # capture can fail on ONE rank only (an allocation, a watchdog race): a rank replaying a graph while another
         # launches eagerly still issues the same collectives in the same order, yet the choice must not depend on
@@ -189,5 +195,8 @@ def run_captured(backend, key, fn, input_ids):
 
 def clear_graphs(backend):
     backend._graphs.clear()
+    smp = getattr(getattr(backend, "model", None), "sampler", None)
+    if smp is not None:
+        smp.captured = False
     if hasattr(backend, "_gstate"):
         backend._gstate.clear()

@@ -244,6 +244,9 @@ class PageTable:
 
 
 class Transformer(nn.Module):
+    sampler = None          # Engine/sampling.Sampler (sampling.attach); None = greedy
+    sample_role = None      # set by the back-end before each step: "prefill" | "baseline" | "draft" | "verify"
+
     def __init__(self, config: ModelArgs):
         super().__init__()
         self.config = config
@@ -682,6 +685,8 @@ class Transformer(nn.Module):
             return None
         logits = self._linear(y, self.output)                         # [rows, vocab / tp]; materialises a deferred norm
         self._last_logits = logits
+        if self.sampler is not None:                                  # Engine/sampling.py: draw instead of argmax
+            return self.sampler.head(logits, self.sample_role, idx, B, n)
         return self._argmax(logits).view(B, n)
 
     def _argmax(self, logits):

@@ -7,12 +7,12 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MAGICDEC_HIP_LIB: development only -- another build of the same sources (e.g. `make TIMING=1`'s instrumented library)
 LIB_PATH = os.environ.get("MAGICDEC_HIP_LIB") or os.path.join(_HERE, "libmagicdec_hip.so")
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _lib = None
 _err = None
@@ -84,6 +84,9 @@ _SIGNATURES = {
     "md_argmax_tp_slots": (c_int, [P, L, I, I, L, I, I, P, P, P]),
     "md_tp_argmax_merge": (c_int, [P, P, I, I, P, P]),
     "md_accept_rollback": (c_int, [P, P, P, I, P, P, P, P, P, I, I, I, I, L, L, L, P, P, P, P, P, P]),
+    "md_philox4x32_10_host": (c_int, [P, I, c_uint32, c_uint32, P]),
+    "md_sample_rows": (c_int, [P, L, I, I, I, c_float, c_float, c_uint64, I, P, P, I, P, P, I, P, P]),
+    "md_spec_verify_sample": (c_int, [P, L, I, I, I, c_float, c_float, c_uint64, P, P, P, P, P, P, P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

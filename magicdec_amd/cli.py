@@ -85,6 +85,38 @@ def baseline_parser():
     return parser
 
 
+def add_sampling_args(parser):
+    """--temperature / --top_p of the five entry points (not in the reference's scripts, whose flags the *_parser()
+    functions above reproduce exactly): temperature 0 (the default) is the greedy loop, unchanged; > 0 samples with the
+    tempered top-p filter and lossless speculative sampling (Engine/sampling.py), seeded by --seed."""
+    parser.add_argument('--temperature', type=float, default=0.0,
+                        help='Sampling temperature; 0 = greedy decoding (default).  TP = 1 only.')
+    parser.add_argument('--top_p', type=float, default=1.0, help='Top-p (nucleus) mass kept when sampling, in (0, 1].')
+    return parser
+
+
+def parse_entry_args(parser, argv=None):
+    """Parse an entry point's command line (the reference's flags + --temperature / --top_p) and validate the sampling
+    flags before anything is loaded."""
+    args = add_sampling_args(parser).parse_args(argv)
+    if not args.temperature >= 0:
+        parser.error(f"--temperature must be >= 0, got {args.temperature}")
+    if not 0 < args.top_p <= 1:
+        parser.error(f"--top_p must be in (0, 1], got {args.top_p}")
+    if args.temperature > 0 and args.rank_group is not None and len(args.rank_group) > 1:
+        parser.error("--temperature > 0 supports one rank only (TP = 1): the vocab-sharded sampler needs cross-rank "
+                     "max / Z / histogram reductions and is not implemented")
+    return args
+
+
+def _sampler(args, engine, gamma, device):
+    """The run's Sampler (None for greedy decoding)."""
+    if args.temperature == 0:
+        return None
+    from .Engine.sampling import Sampler
+    return Sampler(args.temperature, args.top_p, args.seed, args.B, gamma, engine.model.output.weight.shape[0], device)
+
+
 def _eot(tokenizer):
     eot_1 = tokenizer.eos_token_id
     eot_2 = tokenizer.unk_token_id if tokenizer.unk_token_id is not None else tokenizer.encode("<|eot_id|>")[-1]
@@ -111,7 +143,7 @@ def _dataset(args, tokenizer, vocab):
 
 def longspec_main(kind: str, argv=None):
     """kind: 'SnapKV' | 'StreamingLLM' -- tests/<kind>/longspec_benchmark.py."""
-    args = longspec_parser(kind).parse_args(argv)
+    args = parse_entry_args(longspec_parser(kind), argv)
     assert args.prefix_len < args.max_len
     assert (args.max_len + 127) // 128 == args.prefix_len // 128 + 1
     if kind == "SnapKV":
@@ -177,6 +209,7 @@ def longspec_main(kind: str, argv=None):
     dataloader = DataLoader(dataset, batch_size=BATCH_SIZE, shuffle=False, drop_last=True)
     num_eval_steps = min(10, len(dataloader))
     bcast = (args.draft_rank_group[0], global_group) if (use_tp and not draft_target_equal) else None
+    sampler = _sampler(args, engine, args.gamma, DEVICE)
     barrier = dist.barrier if use_tp else None
 
     total_time, num_gen_tokens, target_steps = 0.0, 0, 0
@@ -186,7 +219,7 @@ def longspec_main(kind: str, argv=None):
             break
         input_ids = batch[0].to(DEVICE)
         st, dt = harness.run_longspec_batch(engine, draft, input_ids, args.gamma, MAX_LEN_TARGET, eot_1, eot_2,
-                                            bcast=bcast, barrier=barrier, timers=timers)
+                                            bcast=bcast, barrier=barrier, timers=timers, sampler=sampler)
         total_time += dt
         target_steps += st.iters
         num_gen_tokens += int(st.num_nodes.sum() - (input_ids.shape[1] + 1) * BATCH_SIZE)
@@ -216,7 +249,7 @@ def longspec_main(kind: str, argv=None):
 
 def selfspec_main(kind: str, argv=None):
     """kind: 'SnapKV' | 'StreamingLLM' -- tests/<kind>/selfspec_benchmark.py."""
-    args = selfspec_parser(kind).parse_args(argv)
+    args = parse_entry_args(selfspec_parser(kind), argv)
     assert args.prefix_len < args.max_len
     assert (args.max_len + 127) // 128 == args.prefix_len // 128 + 1
     assert (args.draft_budget - 1) % 128 == 0
@@ -258,6 +291,7 @@ def selfspec_main(kind: str, argv=None):
     dataset = _dataset(args, tokenizer, engine.model.tok_embeddings.weight.shape[0])
     dataloader = DataLoader(dataset, batch_size=BATCH_SIZE, shuffle=False, drop_last=True)
     num_eval_steps = min(10, len(dataloader))
+    sampler = _sampler(args, engine, args.gamma, DEVICE)
     total_time, num_gen_tokens, target_steps = 0.0, 0, 0
     timers = harness.PhaseTimers(DEVICE) if args.benchmark else None
     for step, batch in enumerate(dataloader):
@@ -265,7 +299,7 @@ def selfspec_main(kind: str, argv=None):
             break
         input_ids = batch[0].to(DEVICE)
         st, dt = harness.run_selfspec_batch(engine, input_ids, args.gamma, MAX_LEN_TARGET, eot_1, eot_2, streaming,
-                                            timers=timers)
+                                            timers=timers, sampler=sampler)
         total_time += dt
         target_steps += st.iters
         num_gen_tokens += int(st.num_nodes.sum() - (input_ids.shape[1] + 1) * BATCH_SIZE)
@@ -291,7 +325,7 @@ def selfspec_main(kind: str, argv=None):
 
 def baseline_main(argv=None):
     """tests/baseline_benchmark.py: the autoregressive denominator of every speedup figure."""
-    args = baseline_parser().parse_args(argv)
+    args = parse_entry_args(baseline_parser(), argv)
     assert args.prefix_len < args.max_len          # tests/baseline_benchmark.py:30-31
     assert args.max_len % 128 == 0
     DEVICE = _device()
@@ -320,12 +354,13 @@ def baseline_main(argv=None):
     dataset = _dataset(args, tokenizer, engine.model.tok_embeddings.weight.shape[0])
     dataloader = DataLoader(dataset, batch_size=args.B, shuffle=False, drop_last=True)
     num_eval_steps = min(10, len(dataloader))
+    sampler = _sampler(args, engine, 0, DEVICE)
     total_time, model_steps = 0.0, 0
     for step, batch in enumerate(dataloader):
         if step >= num_eval_steps:
             break
         input_ids = batch[0].to(DEVICE)
-        output, steps, dt = harness.run_baseline_batch(engine, input_ids, args.max_len, eot_1, eot_2)
+        output, steps, dt = harness.run_baseline_batch(engine, input_ids, args.max_len, eot_1, eot_2, sampler=sampler)
         total_time += dt
         model_steps += steps
         if args.printoutput:

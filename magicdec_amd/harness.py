@@ -20,6 +20,7 @@ from dataclasses import dataclass, field
 import torch
 
 from . import ops
+from .Engine import sampling
 
 
 @dataclass
@@ -155,11 +156,14 @@ def check_collectives(*engines):
         ar.check(collective=True)
 
 
-def _draft_round(step_fn, st: LoopState, gamma, next_double):
+def _draft_round(step_fn, st: LoopState, gamma, next_double, sampler=None):
     """gamma draft steps; after an all-accept iteration the first step consumes two tokens
-    (tests/SnapKV/longspec_benchmark.py:165-188)."""
+    (tests/SnapKV/longspec_benchmark.py:165-188).  With a sampler, the two-token step draws only from the row the
+    gather below reads (the sampler's persistent row selector)."""
     for i in range(gamma):
         if i == 0 and next_double:
+            if sampler is not None:
+                sampler.row_sel.copy_(st.cachelens_update)
             nt = step_fn(st.double_buffer, st.cachelens_update)
             st.tokens_buffer[:, 1:2] = nt.gather(1, st.cachelens_update.view(-1, 1) - 1)
         else:
@@ -179,7 +183,7 @@ def _iterate(engine, draft, st: LoopState, body, forced):
 
 
 def longspec_iteration(engine, draft, st: LoopState, gamma, eot_1, eot_2, max_nodes, next_double,
-                       forced_accept=None, bcast=None, timers: PhaseTimers = None):
+                       forced_accept=None, bcast=None, timers: PhaseTimers = None, sampler=None):
     """One iteration of the longspec loop: gamma draft steps, one verify, the fused accept/rollback.
     Returns (terminal, next_double).
 
@@ -190,7 +194,7 @@ def longspec_iteration(engine, draft, st: LoopState, gamma, eot_1, eot_2, max_no
         if timers is not None:
             timers.start()
         if draft is not None:
-            _draft_round(lambda ids, cu: draft.inference(ids, cachelen_update=cu), st, gamma, next_double)
+            _draft_round(lambda ids, cu: draft.inference(ids, cachelen_update=cu), st, gamma, next_double, sampler)
         if bcast is not None:
             import torch.distributed as dist
             dist.broadcast(st.tokens_buffer, src=bcast[0], group=bcast[1])
@@ -213,14 +217,14 @@ def longspec_iteration(engine, draft, st: LoopState, gamma, eot_1, eot_2, max_no
 
 
 def selfspec_iteration(engine, st: LoopState, gamma, eot_1, eot_2, max_nodes, next_double, streaming,
-                       forced_accept=None, timers: PhaseTimers = None):
+                       forced_accept=None, timers: PhaseTimers = None, sampler=None):
     """One iteration of tests/SnapKV/selfspec_benchmark.py:121-211 (streaming=False: draft rolled back by
     gamma+1 and advanced by accept_nums, no two-token step) or tests/StreamingLLM/selfspec_benchmark.py:121-238."""
     def body(forced):
         if timers is not None:
             timers.start()
         if streaming:
-            _draft_round(lambda ids, cu: engine.speculate(ids, cachelen_update=cu), st, gamma, next_double)
+            _draft_round(lambda ids, cu: engine.speculate(ids, cachelen_update=cu), st, gamma, next_double, sampler)
         else:
             _draft_round(lambda ids, cu: engine.speculate(ids), st, gamma, False)
         if timers is not None:
@@ -259,9 +263,13 @@ def _force_accept(tokens_buffer, target_tokens, forced_accept, gamma):
 
 
 def run_longspec_batch(engine, draft, input_ids, gamma, max_len, eot_1, eot_2, forced_accept_fn=None,
-                       trace_fn=None, bcast=None, barrier=None, timers: PhaseTimers = None):
-    """A whole batch: prefill both models, loop until termination.  Returns (state, seconds in the loop)."""
+                       trace_fn=None, bcast=None, barrier=None, timers: PhaseTimers = None, sampler=None):
+    """A whole batch: prefill both models, loop until termination.  Returns (state, seconds in the loop).
+    sampler (Engine/sampling.Sampler, shared by target and draft): temperature / top-p speculative sampling instead of
+    greedy decoding; None (default) is the greedy loop."""
     B, S = input_ids.shape
+    sampling.attach(engine, sampler)
+    sampling.attach(draft, sampler)
     st = new_state(B, gamma, max_len + 1, input_ids.device, input_ids)
     st.tokens_buffer[:, :1] = engine.encode(input_ids=input_ids)[:, -1:]
     if draft is not None:
@@ -273,7 +281,8 @@ def run_longspec_batch(engine, draft, input_ids, gamma, max_len, eot_1, eot_2, f
     terminal, nd = False, False
     while not terminal:
         fa = forced_accept_fn(st) if forced_accept_fn is not None else None
-        terminal, nd = longspec_iteration(engine, draft, st, gamma, eot_1, eot_2, S + 80, nd, fa, bcast, timers)
+        terminal, nd = longspec_iteration(engine, draft, st, gamma, eot_1, eot_2, S + 80, nd, fa, bcast, timers,
+                                          sampler)
         if trace_fn is not None:
             trace_fn(st)
     _sync(input_ids)
@@ -285,8 +294,9 @@ def run_longspec_batch(engine, draft, input_ids, gamma, max_len, eot_1, eot_2, f
 
 
 def run_selfspec_batch(engine, input_ids, gamma, max_len, eot_1, eot_2, streaming, forced_accept_fn=None,
-                       trace_fn=None, timers: PhaseTimers = None):
+                       trace_fn=None, timers: PhaseTimers = None, sampler=None):
     B, S = input_ids.shape
+    sampling.attach(engine, sampler)
     st = new_state(B, gamma, max_len + 1, input_ids.device, input_ids)
     st.tokens_buffer[:, :1] = engine.encode(input_ids=input_ids)[:, -1:]
     if streaming:
@@ -296,7 +306,8 @@ def run_selfspec_batch(engine, input_ids, gamma, max_len, eot_1, eot_2, streamin
     terminal, nd = False, False
     while not terminal:
         fa = forced_accept_fn(st) if forced_accept_fn is not None else None
-        terminal, nd = selfspec_iteration(engine, st, gamma, eot_1, eot_2, S + 80, nd, streaming, fa, timers)
+        terminal, nd = selfspec_iteration(engine, st, gamma, eot_1, eot_2, S + 80, nd, streaming, fa, timers,
+                                          sampler)
         if trace_fn is not None:
             trace_fn(st)
     _sync(input_ids)
@@ -307,8 +318,9 @@ def run_selfspec_batch(engine, input_ids, gamma, max_len, eot_1, eot_2, streamin
     return st, dt
 
 
-def run_baseline_batch(engine, input_ids, max_len, eot_1, eot_2, check_eot_every=1):
-    """tests/baseline_benchmark.py:72-90: greedy autoregressive decode until max_len or EOT."""
+def run_baseline_batch(engine, input_ids, max_len, eot_1, eot_2, check_eot_every=1, sampler=None):
+    """tests/baseline_benchmark.py:72-90: greedy autoregressive decode until max_len or EOT (sampled with a sampler)."""
+    sampling.attach(engine, sampler)
     output = input_ids.clone()
     next_tokens = engine.encode(input_ids=input_ids)[:, -1:]
     output = torch.cat((output, next_tokens), dim=-1)

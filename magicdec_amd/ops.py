@@ -764,3 +764,83 @@ def accept_rollback(tokens_buffer, target_tokens, output, num_nodes, cachelens, 
                                  gamma, draft_rollback, draft_cap, int(eot_1), int(eot_2), int(max_nodes),
                                  _p(accept_nums), _p(bonus), _p(double_buffer), _p(cachelens_update), _p(flags),
                                  _stream()), "md_accept_rollback")
+
+
+# ------------------------------------------------------------------ K11 sampling (include/magicdec_hip.h)
+SAMPLE_PREFILL, SAMPLE_BASELINE, SAMPLE_DRAFT, SAMPLE_ACCEPT, SAMPLE_RESIDUAL, SAMPLE_BONUS = range(6)
+ADVANCE_NONE, ADVANCE_STEP, ADVANCE_ITER = 0, 1, 2
+STATS_WORDS = 2          # md_sample_stats = 16 bytes = two int64 words per row
+
+
+def _sample_args(logits, temperature, top_p):
+    if logits.dim() != 2 or logits.stride(1) != 1 or logits.dtype != torch.bfloat16:
+        raise ValueError("sampling expects bf16 logits [rows, vocab] with unit inner stride")
+    if not (temperature > 0 and 0 < top_p <= 1):
+        raise ValueError(f"sampling needs temperature > 0 and 0 < top_p <= 1, got {temperature}, {top_p}")
+
+
+def sample_rows(logits, n, temperature, top_p, seed, purpose, counters, advance, row_sel=None, ring=None,
+                ring_stats=None, out=None):
+    """Tempered top-p Gumbel-max draw of ONE row per request from logits [B*n, vocab] bf16 (row row_sel[b]-1 of the
+    request, else its last row); returns tokens [B, n] int64 with the token in every column.  counters: int32 [4] on the
+    device (iteration, draft step, ticket, -).  Draft mode (ring [B, gamma, vocab] bf16, ring_stats [B, gamma, 2] int64):
+    the row and its stats also go to ring slot counters[1]."""
+    _gpu(logits, counters)
+    _sample_args(logits, temperature, top_p)
+    rows, vocab = logits.shape
+    if rows % n:
+        raise ValueError(f"sample_rows: {rows} rows are not B x n = {n}")
+    B = rows // n
+    gamma = 0
+    if ring is not None:
+        _gpu(ring, ring_stats)
+        if ring.shape[0] != B or ring.shape[2] != vocab or not ring.is_contiguous() or ring.dtype != torch.bfloat16:
+            raise ValueError(f"sample_rows: the draft ring must be a contiguous bf16 [B={B}, gamma, vocab={vocab}] tensor "
+                             f"(draft and target vocabularies must be equal); got {tuple(ring.shape)}")
+        gamma = ring.shape[1]
+        if tuple(ring_stats.shape) != (B, gamma, STATS_WORDS) or not ring_stats.is_contiguous():
+            raise ValueError("sample_rows: ring_stats must be a contiguous [B, gamma, 2] int64 tensor")
+    if row_sel is not None:
+        _gpu(row_sel)
+        if row_sel.dtype != torch.int64 or row_sel.numel() != B or not row_sel.is_contiguous():
+            raise ValueError("sample_rows: row_sel must be a contiguous int64 [B] tensor")
+    if out is None:
+        out = torch.empty((B, n), dtype=torch.int64, device=logits.device)
+    check(_lib.load().md_sample_rows(_p(logits), logits.stride(0), B, n, vocab, float(temperature), float(top_p),
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF, int(purpose), _p(row_sel), _p(counters),
+                                     int(advance), _p(ring), _p(ring_stats), gamma, _p(out), _stream()),
+          "md_sample_rows")
+    return out
+
+
+def spec_verify_sample(logits, tokens_buffer, ring, ring_stats, target_stats, counters, temperature, top_p, seed,
+                       out=None):
+    """Speculative-sampling verify: target logits [B*(gamma+1), vocab] bf16, the draft ring / stats of this iteration and
+    tokens_buffer [B, gamma+1] -> target_tokens [B, gamma+1] int64 in the encoding ops.accept_rollback consumes
+    unchanged.  target_stats: [B*(gamma+1), 2] int64 workspace (holds the target rows' stats afterwards)."""
+    _gpu(logits, tokens_buffer, ring, ring_stats, target_stats, counters)
+    _sample_args(logits, temperature, top_p)
+    B, G1 = tokens_buffer.shape
+    rows, vocab = logits.shape
+    if rows != B * G1 or tuple(ring.shape) != (B, G1 - 1, vocab) or ring.dtype != torch.bfloat16:
+        raise ValueError(f"spec_verify_sample: logits {tuple(logits.shape)}, ring {tuple(ring.shape)} and tokens_buffer "
+                         f"{tuple(tokens_buffer.shape)} disagree (draft and target vocabularies must be equal)")
+    if tuple(target_stats.shape) != (rows, STATS_WORDS) or tuple(ring_stats.shape) != (B, G1 - 1, STATS_WORDS):
+        raise ValueError("spec_verify_sample: stats tensors must be [rows, 2] / [B, gamma, 2] int64")
+    if out is None:
+        out = torch.empty((B, G1), dtype=torch.int64, device=logits.device)
+    check(_lib.load().md_spec_verify_sample(_p(logits), logits.stride(0), B, G1 - 1, vocab, float(temperature),
+                                            float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(tokens_buffer.contiguous()),
+                                            _p(ring), _p(ring_stats), _p(target_stats), _p(counters), _p(out),
+                                            _stream()), "md_spec_verify_sample")
+    return out
+
+
+def philox_host(counters, key0, key1):
+    """Philox4x32-10 of the library (host): counters uint32-valued [n, 4] -> [n, 4] words (numpy uint32 arrays)."""
+    import numpy as np
+    c = np.ascontiguousarray(counters, dtype=np.uint32).reshape(-1, 4)
+    out = np.empty_like(c)
+    check(_lib.load().md_philox4x32_10_host(c.ctypes.data, c.shape[0], int(key0) & 0xFFFFFFFF,
+                                            int(key1) & 0xFFFFFFFF, out.ctypes.data), "md_philox4x32_10_host")
+    return out
