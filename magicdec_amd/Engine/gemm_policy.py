@@ -26,8 +26,10 @@ every decode / verify shape of the BASELINE models timed on both, weights cycled
     and NOT the narrow projections, where splitting K over ~256 workgroups costs a partial-sum round trip the product is
     too small to pay for (wqkv 30-32 vs lib 27 + 6.3 for rope/append: a wash; wo 34-35 vs 25; every TP8 shard slower).
 
-A weight a hand-written kernel will serve is re-packed once at setup_caches (Transformer._pack_weights); the row-major
-copy stays for the prefill-sized products.  MAGICDEC_GEMM=hip forces md_linear wherever it supports the shape,
+These rules are shape policy only.  Engine/model_core.plan_linear is the one place that combines them with the kernels'
+shape-support queries into "which implementation runs this linear of a step"; the step executes from its answer, and the
+choice of weights to re-pack once at setup_caches (Transformer._pack_weights) and of row-major tensors to release after
+prefill is predicted from the same answer.  The row-major copy stays for the prefill-sized products.  MAGICDEC_GEMM=hip forces md_linear wherever it supports the shape,
 MAGICDEC_GEMM=lib forces the library, MAGICDEC_FUSED=0/1 switches md_linear_fused off / on everywhere (the A/B
 switches)."""
 import os
@@ -107,12 +109,15 @@ def set_packed_copies(mode: str):
     _PACKED = mode
 
 
-def want_packed(N: int, K: int, swiglu: bool = False, int8: bool = False, rows=None) -> bool:
+def packed_copies_mode() -> str:
+    return _PACKED
+
+
+def want_packed(N: int, K: int, swiglu: bool = False, int8: bool = False) -> bool:
     """Re-pack this weight into the streaming layout at load time?  Only when a hand-written kernel may actually be
-    chosen for it at some row count of a decode / verify step: `rows` = the counts the engine will run (the back-end knows
-    them: batch x {1, 2, dec_len}), or None = any of 1..256 (round 3 packed every bf16 weight with
-    K % 128 == 0; round 6: the 8B wqkv, served by the library at 64 and 256 rows, is no longer packed for the 32-row
-    steps configs[2] never runs)."""
+    chosen for it at some row count 1..256 of a decode / verify step (round 3 packed every bf16 weight with
+    K % 128 == 0).  An engine that knows its steps' row counts asks Transformer._wants_packed instead (round 6: the 8B
+    wqkv, served by the library at 64 and 256 rows, is no longer packed for the 32-row steps configs[2] never runs)."""
     if _MODE == "lib" or _PACKED == "0" or K % 64:
         return False
     if int8:
@@ -120,8 +125,7 @@ def want_packed(N: int, K: int, swiglu: bool = False, int8: bool = False, rows=N
     if _MODE == "hip" or _BLOCK == "1" or _FUSED == "1" or _SPLIT == "1":
         return True
     kinds = ("swiglu",) if swiglu else ("plain", "resid", "qkv")
-    for M in ((1,) + tuple(range(32, 257, 32)) if rows is None else tuple(m for m in rows if m <= 256)):
-        # (default: every 32-row tile count a rule can depend on -- ADVICE r4)
+    for M in (1,) + tuple(range(32, 257, 32)):          # every 32-row tile count a rule can depend on
         if use_skinny(M, N, K, swiglu, False, True):
             return True
         for kind in kinds:

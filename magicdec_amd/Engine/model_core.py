@@ -10,8 +10,9 @@ token ids [B, n].  What differs from the reference is everything underneath:
 * no flashinfer, no torch.library ops, no torch.compile: the attention, RoPE,
   KV append, SnapKV select, StreamingLLM eviction, norms, SiLU*mul and argmax
   are hand-written gfx950 kernels reached through the C ABI (magicdec_amd.ops);
-* per layer and step: 4 linears (w1|w3 fused into one) -- each on the kernel the
-  measured policy of Engine/gemm_policy.py picks: md_linear_fused (launch-bound small
+* per layer and step: 4 linears (w1|w3 fused into one) -- each on the kernel `plan_linear` below answers (the ONE
+  place where the measured policy of Engine/gemm_policy.py meets the kernels' shape support; the step's executors
+  and the weight-release prediction both read it): md_linear_fused (launch-bound small
   products: the product AND its consumer -- rope+append, residual add, SiLU*mul, the
   RMSNorm in front -- in one launch: a 1B draft layer is 5-7 launches), md_linear (long
   weight streams; its split-K combine also adds the residual and normalises) or
@@ -243,6 +244,62 @@ class PageTable:
     max_pages: int  # host upper bound of pages per request
 
 
+@dataclass(frozen=True)
+class LinearPlan:
+    """What runs one linear of a step (the answer of `plan_linear`)."""
+    how: str                       # "fused_qkv" | "fused" | "split" | "block" | "skinny" | "lib"
+    absorbs_norm: bool = False     # applies the deferred RMSNorm on its input itself (no stand-alone norm launch)
+    add_norm: bool = False         # an `*_add_rmsnorm` form: its combine launch adds the residual and normalises
+    defers_norm: bool = False      # fused residual epilogue: the norm of its OUTPUT is left to the consumer
+
+
+def plan_linear(site, M, N, K, int8, packed, tp, deferred, head_dim, guards=True) -> LinearPlan:
+    """Which implementation runs the linear [N, K] at `site` of a step of M rows.  The only place of this module where the
+    policy (Engine/gemm_policy.py) and the kernels' shape-support queries meet: `_std_step`, `_proj_add_norm` and `_linear`
+    dispatch on its answer, `Transformer._step_hows` (which weights get / keep which layout) predicts from it.
+
+    site: "wqkv"; "proj" (wo / w2: output projection + residual add + the next RMSNorm); "w13" (w1|w3 + SiLU*mul);
+    "plain" (the lm head, and what `_linear` runs for a wqkv / proj that did not take an epilogue form).
+    packed: a streaming-layout copy exists; tp: tensor parallel (the projection's sum is all-reduced before the add);
+    deferred: the input arrives as an `ops.DeferredNorm`.
+    guards: the runtime-only guards the site evaluates hold -- operands on the GPU with unit inner stride, a contiguous
+    residual, the same number of rows for every request, no fp8 calibration pending.  False: no epilogue form at wqkv /
+    proj (the answer is then the plain one, for `_linear`, which evaluates its own guard) and the library at w13 / plain."""
+    from .gemm_policy import choose, skinny_absorbs_norm, use_split
+    tile = packed and not int8            # the tile / block kernels stream bf16 PackedWeights only
+    if site == "wqkv":
+        # (deferred RMSNorm +) wqkv + bias + RoPE + paged append in one launch
+        if (guards and tile and head_dim in (64, 128) and choose(M, N, K, False, False, True, "qkv", deferred) == "fused"
+                and ops.fused_linear_supported(M, N, K)):
+            return LinearPlan("fused_qkv", absorbs_norm=deferred)
+        site, deferred, guards = "plain", False, True          # anything else ("block" too): norm materialised, `_linear`
+    elif site == "proj":
+        if guards and not tp:
+            if tile and choose(M, N, K, False, False, True, "resid") == "fused" and ops.fused_linear_supported(M, N, K):
+                return LinearPlan("fused", defers_norm=True)
+            if tile and use_split(M, N, K, "resid") and ops.fused_split_supported(M, N, K):
+                # deep narrow projection of a draft step (the 1B w2): the tile kernel with K split over workgroups
+                return LinearPlan("split", add_norm=True)
+            how = choose(M, N, K, False, int8, packed, "resid")
+            if how == "block" and ops.linear_block_supported(M, N, K):
+                return LinearPlan("block", add_norm=True)
+            if how in ("skinny", "block") and ops.linear_add_rmsnorm_supported(M, N, K):
+                return LinearPlan("skinny", add_norm=True)
+        site, deferred, guards = "plain", False, True          # `_linear` (policy kind "plain"), then `_reduce_add_norm`
+    if not guards:
+        return LinearPlan("lib")
+    swiglu = site == "w13"
+    how = choose(M, N, K, swiglu, int8, packed, "swiglu" if swiglu else "plain", deferred and swiglu)
+    if how == "fused" and ops.fused_linear_supported(M, N, K):
+        return LinearPlan("fused", absorbs_norm=deferred and swiglu)
+    if how == "block" and ops.linear_block_supported(M, N, K, swiglu):
+        return LinearPlan("block")
+    if how in ("fused", "skinny", "block") and ops.linear_supported(M, N, K, swiglu):
+        # the weight-streaming kernel normalises its activation slabs on the way to LDS (md_linear_normed)
+        return LinearPlan("skinny", absorbs_norm=deferred and not int8 and skinny_absorbs_norm(M))
+    return LinearPlan("lib")
+
+
 class Transformer(nn.Module):
     sampler = None          # Engine/sampling.Sampler (sampling.attach); None = greedy
     sample_role = None      # set by the back-end before each step: "prefill" | "baseline" | "draft" | "verify"
@@ -262,6 +319,13 @@ class Transformer(nn.Module):
         # optional static fp8 KV scales [(k_scale[KH], v_scale[KH]) per layer], e.g. from an offline calibration;
         # when set they replace the first-chunk calibration of every encode()
         self.kv_scale_override = None
+        # streaming-layout copies (_pack_weights), keyed by id(row-major weight)
+        self._packed = {}               # -> ops.PackedWeight
+        self._by_id = {}                # -> the row-major weight
+        self._roles = {}                # -> (role, layer index | None)
+        self._released = set()          # ids whose row-major tensor is currently released (release_rowmajor)
+        self._last_M = None             # rows of the latest _linear call (for _resident's report)
+        self._warned_transient = False
 
     @classmethod
     def from_name(cls, name: str):
@@ -326,14 +390,11 @@ class Transformer(nn.Module):
         steps -- md_linear for the long weight streams, md_linear_fused for the launch-bound small products
         (Engine/gemm_policy.py); keyed by the id of the row-major tensor the step would otherwise use.  The row-major
         tensors stay for the prefill-sized library GEMMs; the extra bytes are reported once (`packed_bytes`)."""
-        from .gemm_policy import want_packed
-        self._packed = {}
-        self._released, self._by_id, self._roles = set(), {}, {}
+        self._packed, self._by_id, self._roles, self._released = {}, {}, {}, set()
         if not self.output.weight.is_cuda and not force:      # force: host tests of the bookkeeping (no kernel runs)
             return
 
         todo = []
-        self._roles = {}                                # id(weight) -> (role, layer index | None)
         for i, b in enumerate(self.layers):
             for w, sw, role in ((self._w13[i], True, "w13"), (b.attention.wqkv.weight, False, "wqkv"),
                                 (b.attention.wo.weight, False, "wo"), (b.feed_forward.w2.weight, False, "w2")):
@@ -379,84 +440,64 @@ class Transformer(nn.Module):
         for w, sw in todo:
             pw = ops.PackedWeight(w.data if isinstance(w, nn.Parameter) else w, swiglu=sw)
             self._packed[id(w)] = pw
-        self._released = set()          # ids of weights whose row-major tensor is currently released (release_rowmajor)
         self._by_id = {id(w): w for w, _ in todo}
 
     @property
     def packed_bytes(self):
         """Bytes of weights held TWICE right now: a streaming-layout copy beside a resident row-major tensor.  After
         release_rowmajor() that is only what decode reads in both layouts (at different row counts)."""
-        pk = getattr(self, "_packed", None)
-        if not pk:
-            return 0
-        rel = getattr(self, "_released", set())
-        return sum(p.data.numel() * p.data.element_size() for k, p in pk.items() if k not in rel)
+        return sum(p.data.numel() * p.data.element_size() for k, p in self._packed.items() if k not in self._released)
 
     @property
     def released_bytes(self):
         """Bytes of row-major weight tensors currently released (their streaming-layout copy is the one resident copy)."""
         return sum(self._by_id[k].shape[0] * self._by_id[k].shape[1] * self._by_id[k].element_size()
-                   for k in getattr(self, "_released", ()))
-
-    @packed_bytes.setter
-    def packed_bytes(self, v):          # legacy assignment in _pack_weights: ignored (the property is computed)
-        pass
+                   for k in self._released)
 
     # ------------------------------------------------------------------ one resident copy per weight (round 6)
-    def _decode_hows(self, role, N, K, int8, M, packed=True):
-        """The implementations a decode / verify step of M rows may run this weight on ("fused" | "split" | "block" |
-        "skinny" | "lib"), assuming a streaming-layout copy exists iff `packed` -- the decisions of _std_step /
-        _proj_add_norm / _linear, through the same policy and shape-support functions, without running anything."""
-        from .gemm_policy import choose, use_split
-        pk = True if packed else None
-        tp = self.process_group is not None
-        l0 = self.layers[0]
+    def _plan(self, site, w, M, deferred=False, guards=True, packed=None):
+        """`plan_linear` for the weight `w` of this model at `site`; `packed`: assume a streaming-layout copy exists (the
+        prediction, which also runs before the copies are made) instead of looking it up."""
+        N, K = w.shape
+        return plan_linear(site, M, N, K, w.dtype == torch.int8, id(w) in self._packed if packed is None else packed,
+                           self.process_group is not None, deferred, self.config.head_dim, guards)
 
-        def resid_fused(w):          # is the residual epilogue (-> a DEFERRED norm for its consumer) taken for this projection?
-            n, k = w.shape
-            return not tp and w.dtype != torch.int8 and self._fused_ok(M, n, k, True, False, "resid", False)
-        if role == "w13":
-            pros = {resid_fused(l0.attention.wo.weight)}                       # its input comes from the wo sub-layer
-            return {self._linear_how(M, N, K, True, int8, pk, "swiglu", pro) for pro in pros}
-        if role == "wqkv":
-            pros = {False, resid_fused(l0.feed_forward.w2.weight)}             # layer 0 reads a materialised norm
-            hows = set()
-            for pro in pros:
-                fused = self.config.head_dim in (64, 128) and self._fused_ok(M, N, K, pk, int8, "qkv", pro)
-                hows.add("fused" if fused else self._linear_how(M, N, K, False, int8, pk, "plain", False))
-            return hows
-        if role in ("wo", "w2"):
-            if not tp and self._fused_ok(M, N, K, pk, int8, "resid", False):
-                return {"fused"}
-            if not tp and pk is not None and not int8 and use_split(M, N, K, "resid") and ops.fused_split_supported(M, N, K):
-                return {"split"}
-            if not tp:
-                how = choose(M, N, K, False, int8, pk is not None, "resid")
-                if how == "block" and ops.linear_block_supported(M, N, K):
-                    return {"block"}
-                if how in ("skinny", "block") and ops.linear_add_rmsnorm_supported(M, N, K):
-                    return {"skinny"}
-        return {self._linear_how(M, N, K, False, int8, pk, "plain", False)}          # wo / w2 fall-through, lm head
+    def _step_hows(self, M):
+        """role ("wqkv" | "wo" | "w13" | "w2" | "head") -> the implementations (LinearPlan.how) a decode / verify step of M
+        rows can run that weight on, streaming-layout copies assumed: a walk over the linears in the order `_run` chains
+        them, carrying the deferred-norm state from each one to its consumer.  All layers share their shapes, so layer 0
+        (which reads a materialised norm) and one later layer cover every layer."""
+        l0 = self.layers[0]
+        chain = (("wqkv", "wqkv", l0.attention.wqkv.weight), ("wo", "proj", l0.attention.wo.weight),
+                 ("w13", "w13", self._w13[0]), ("w2", "proj", l0.feed_forward.w2.weight))
+        hows = {role: set() for role in ("wqkv", "wo", "w13", "w2", "head")}
+        deferred = False
+        for _ in range(2):
+            for role, site, w in chain:
+                plan = self._plan(site, w, M, deferred, packed=True)
+                hows[role].add(plan.how)
+                deferred = plan.defers_norm
+        hows["head"].add(self._plan("plain", self.output.weight, M, deferred, packed=True).how)
+        return hows
 
     def _wants_packed(self, role, w):
         """A streaming-layout copy of this weight?  With known decode row counts: iff some step of this engine runs it on a
         hand-written kernel; unknown: gemm_policy.want_packed (any row count 1..256)."""
-        from .gemm_policy import want_packed, _MODE, _PACKED
+        from .gemm_policy import mode, packed_copies_mode, want_packed
         N, K = w.shape
         int8 = w.dtype == torch.int8
-        if self.decode_rows is None or _MODE != "auto" or int8:
+        if self.decode_rows is None or mode() != "auto" or int8:
             return want_packed(N, K, role == "w13", int8)
-        if _PACKED == "0" or K % 64:
+        if packed_copies_mode() == "0" or K % 64:
             return False
-        return any(self._decode_hows(role, N, K, int8, M) - {"lib"} for M in self.decode_rows if M <= 256)
+        return any(self._step_hows(M)[role] - {"lib"} for M in self.decode_rows if M <= 256)
 
     def _rowmajor_in_decode(self, w):
         """Does some decode / verify step of this engine hand the ROW-MAJOR tensor of `w` to a kernel (the library GEMM)?"""
         role, _ = self._roles[id(w)]
         if self._packed.get(id(w)) is None or w.dtype == torch.int8 or self.decode_rows is None:
             return True
-        N, K = w.shape
-        return any(M > 256 or "lib" in self._decode_hows(role, N, K, False, M) for M in self.decode_rows)
+        return any(M > 256 or "lib" in self._step_hows(M)[role] for M in self.decode_rows)
 
     def release_rowmajor(self):
         """After prefill: free the row-major tensor of every weight that decode only ever reads in the streaming layout
@@ -465,7 +506,7 @@ class Transformer(nn.Module):
         restore_rowmajor() re-materialises them from the streaming copy before the next prefill.  MAGICDEC_KEEP_ROWMAJOR=1
         switches this off."""
         import os
-        if not getattr(self, "_packed", None) or os.environ.get("MAGICDEC_KEEP_ROWMAJOR", "0") == "1":
+        if not self._packed or os.environ.get("MAGICDEC_KEEP_ROWMAJOR", "0") == "1":
             return 0
         freed = 0
         for k, w in self._by_id.items():
@@ -488,7 +529,7 @@ class Transformer(nn.Module):
 
     def restore_rowmajor(self):
         """Before a prefill: every released row-major tensor back from its streaming-layout copy (one permute each)."""
-        for k in list(getattr(self, "_released", ())):
+        for k in list(self._released):
             w = self._by_id[k]
             rows = self._packed[k].unpack().contiguous()
             role, i = self._roles[k]
@@ -505,11 +546,11 @@ class Transformer(nn.Module):
     def _resident(self, w):
         """The row-major tensor of `w` for a library GEMM; a released one is unpacked for this call only (a decode step the
         policy prediction did not foresee: correct, slow, and reported once)."""
-        if id(w) in getattr(self, "_released", ()):
-            if not getattr(self, "_warned_transient", False):
+        if id(w) in self._released:
+            if not self._warned_transient:
                 self._warned_transient = True
                 print(f"[magicdec_amd] a library GEMM needs the released row-major weight {tuple(w.shape)} in a decode step "
-                      f"of {getattr(self, '_last_M', '?')} rows (not among decode_rows={self.decode_rows}): unpacked per call")
+                      f"of {self._last_M} rows (not among decode_rows={self.decode_rows}): unpacked per call")
             return self._packed[id(w)].unpack()
         return w
 
@@ -526,142 +567,87 @@ class Transformer(nn.Module):
                 dist.all_reduce(y, group=group)
         return y
 
-    def _linear(self, x2d, lin, swiglu_w13=None, resid=None, want_ssq=False):
-        """One linear of a step.  Four implementations, chosen per shape by the measured rules of
-        Engine/gemm_policy.py: md_linear_fused (csrc/tilegemm.hip: the launch-bound small products -- draft-model
-        linears, tensor-parallel shards -- in one launch together with their epilogue), md_linear_block
-        (csrc/blockgemm.hip: the wide 129..256-row products of a verify step), md_linear (csrc/gemm.hip: the long weight
-        streams at <= 128 rows, split-K + combine) or the library GEMM (prefill-sized M, and whatever the A/B gave it).
+    def _linear(self, x2d, lin, swiglu_w13=None):
+        """One linear of a step on the implementation `plan_linear` answers for it (site "w13" or "plain"):
+        md_linear_fused (csrc/tilegemm.hip: the launch-bound small products -- draft-model linears, tensor-parallel
+        shards -- in one launch together with their epilogue), md_linear_block (csrc/blockgemm.hip: the wide 129..256-row
+        products of a verify step), md_linear (csrc/gemm.hip: the long weight streams at <= 128 rows, split-K + combine)
+        or the library GEMM (prefill-sized M, and whatever the A/B gave it).
         `swiglu_w13 = (w13, s13)`: the fused w1|w3 product with the SiLU*mul epilogue.
-        `resid`: return bf16(resid + linear) instead (the residual add of the block; only honoured by the fused
-        kernel -- callers check `_fused_here` first); with `want_ssq` also the per-row partial sums of squares of the
-        result (the producer half of a deferred RMSNorm).  `x2d` may be an `ops.DeferredNorm`: the fused w1|w3 kernel
-        applies it on the fly, every other path materialises it first."""
-        from .gemm_policy import choose, skinny_absorbs_norm
+        `x2d` may be an `ops.DeferredNorm`: a kernel the plan lets absorb it applies it on the fly, every other one gets
+        the materialised rows."""
         if swiglu_w13 is not None:
             w, scales, bias = swiglu_w13[0], swiglu_w13[1], None
         else:
             w, scales, bias = lin.weight, getattr(lin, "scales", None), lin.bias
+        swiglu = swiglu_w13 is not None
         pro = x2d if isinstance(x2d, ops.DeferredNorm) else None      # a norm still to be applied to the input
         if pro is not None:
             x2d = pro.h
-        M, K = x2d.shape
-        N = w.shape[0]
-        self._last_M = M
-        swiglu = swiglu_w13 is not None
+        self._last_M = x2d.shape[0]
+        plan = self._plan("w13" if swiglu else "plain", w, x2d.shape[0], pro is not None, guards=x2d.is_cuda)
+        if pro is not None and not plan.absorbs_norm:
+            x2d, pro = pro.materialize(), None
         pk = self._packed.get(id(w))
-        kind = "swiglu" if swiglu else ("resid" if resid is not None else "plain")
-        how = (choose(M, N, K, swiglu, w.dtype == torch.int8, pk is not None, kind, pro is not None and swiglu)
-               if x2d.is_cuda else "lib")
-        if how == "fused" and ops.fused_linear_supported(M, N, K):
-            if pro is not None and not swiglu:
-                x2d, pro = pro.materialize(), None
-            return ops.fused_linear(x2d, pk, bias, swiglu=swiglu, resid=resid, want_ssq=want_ssq, pro=pro)
-        assert resid is None, "the residual epilogue exists on the fused kernel only"
-        skinny = how in ("fused", "skinny", "block") and ops.linear_supported(M, N, K, swiglu)
-        if how == "block" and ops.linear_block_supported(M, N, K, swiglu):
-            skinny = False
-        if pro is not None and skinny and w.dtype == torch.bfloat16 and skinny_absorbs_norm(M):
-            # the weight-streaming kernel normalises its activation slabs on the way to LDS (md_linear_normed)
-            return ops.linear(x2d, pk if pk is not None else w, bias, None, swiglu, self.workspace, pro=pro)
-        if pro is not None:
-            x2d = pro.materialize()
-        if how == "block" and ops.linear_block_supported(M, N, K, swiglu):
+        if plan.how == "fused":
+            return ops.fused_linear(x2d, pk, bias, swiglu=swiglu, pro=pro)
+        if plan.how == "block":
             return ops.linear_block(x2d, pk, bias, swiglu, self.workspace)
-        if skinny:
-            return ops.linear(x2d, pk if pk is not None else w, bias, scales, swiglu, self.workspace)
+        if plan.how == "skinny":
+            return ops.linear(x2d, pk if pk is not None else w, bias, scales, swiglu, self.workspace, pro=pro)
         if w.dtype == torch.int8:      # WeightOnlyInt8Linear.forward (Engine/quantize.py:84-86), dequantised on the fly
             h = F.linear(x2d, w.to(dtype=x2d.dtype)) * scales
         else:
             h = F.linear(x2d, self._resident(w), bias)
         if swiglu:
-            inter = N // 2
+            inter = w.shape[0] // 2
             return ops.silu_mul(h[:, :inter], h[:, inter:])
         return h
 
-    def _linear_how(self, M, N, K, swiglu, int8, pk, kind, has_pro):
-        """Which implementation `_linear` ends up on for this shape: "fused" | "block" | "skinny" | "lib" -- the same
-        sequence of policy and shape-support checks, without running anything (release_rowmajor's prediction)."""
-        from .gemm_policy import choose
-        how = choose(M, N, K, swiglu, int8, pk is not None, kind, has_pro and swiglu)
-        if how == "fused" and ops.fused_linear_supported(M, N, K):
-            return "fused"
-        if how == "block" and ops.linear_block_supported(M, N, K, swiglu):
-            return "block"
-        if how in ("fused", "skinny", "block") and ops.linear_supported(M, N, K, swiglu):
-            return "skinny"
-        return "lib"
-
-    def _fused_ok(self, M, N, K, pk, int8, kind, absorbs_norm):
-        from .gemm_policy import choose
-        return (pk is not None and not int8 and choose(M, N, K, False, False, True, kind, absorbs_norm) == "fused"
-                and ops.fused_linear_supported(M, N, K))
-
-    def _fused_here(self, x2d, w, kind, absorbs_norm=False):
-        """Does the fused kernel serve the linear `w` with epilogue `kind` ("qkv" | "resid") for these rows?
-        (policy + shape support + a packed bf16 copy)"""
-        from .gemm_policy import choose
-        M, K = x2d.shape
-        N = w.shape[0]
-        pk = self._packed.get(id(w))
-        return (x2d.is_cuda and pk is not None and w.dtype != torch.int8
-                and choose(M, N, K, False, False, True, kind, absorbs_norm) == "fused"
-                and ops.fused_linear_supported(M, N, K))
-
-    def _proj_add_norm(self, inp, lin, x, norm, group):
+    def _proj_add_norm(self, inp, lin, x, norm):
         """Output projection of a sub-layer (wo / w2), the residual add and the RMSNorm for the next sub-layer:
-        (h, y) = (x + sum_ranks(inp . W^T), rmsnorm(h) * w).  Without tensor parallelism and on a launch-bound shape the
-        projection and the residual add are one launch (md_linear_fused, MD_FL_RESID) and y is returned as an
-        `ops.DeferredNorm`; otherwise the projection, then `_reduce_add_norm` (collective + fused add + norm)."""
-        if group is None and x.is_contiguous() and self._fused_here(inp, lin.weight, "resid"):
-            # the norm is DEFERRED: the residual epilogue leaves the per-row partial sums of squares, and the linear that
-            # consumes the normalised rows (w1|w3, the next layer's wqkv) applies rmsnorm on the fly; a consumer that
-            # cannot (library GEMM, lm head) materialises it with the stand-alone kernel
-            h, ssq = self._linear(inp, lin, resid=x, want_ssq=True)
+        (h, y) = (x + sum_ranks(inp . W^T), rmsnorm(h) * w), on what `plan_linear` answers for site "proj": the projection
+        and the residual add in one launch (md_linear_fused, MD_FL_RESID) with y returned as an `ops.DeferredNorm`; a
+        split-K kernel whose combine launch also adds the residual and normalises; or the projection through `_linear`,
+        then `_reduce_add_norm` (collective + fused add + norm)."""
+        w = lin.weight
+        plan = self._plan("proj", w, inp.shape[0], guards=inp.is_cuda and inp.stride(-1) == 1 and x.is_contiguous())
+        pk = self._packed.get(id(w))
+        if plan.defers_norm:
+            # the residual epilogue leaves the per-row partial sums of squares, and the linear that consumes the normalised
+            # rows (w1|w3, the next layer's wqkv) applies rmsnorm on the fly; a consumer that cannot (library GEMM, the
+            # lm head above 64 rows) materialises it with the stand-alone kernel
+            h, ssq = ops.fused_linear(inp, pk, lin.bias, resid=x, want_ssq=True)
             return h, ops.DeferredNorm(h, ssq, norm.weight, norm.eps)
-        if group is None and inp.is_cuda and x.stride(-1) == 1:
-            # the weight-streaming kernel's split-K combine launch also adds the residual and normalises
-            from .gemm_policy import choose, use_split
-            w = lin.weight
-            M, K = inp.shape
-            pk = self._packed.get(id(w))
-            if (pk is not None and w.dtype == torch.bfloat16 and inp.stride(-1) == 1
-                    and use_split(M, w.shape[0], K, "resid") and ops.fused_split_supported(M, w.shape[0], K)):
-                # deep narrow projection of a draft step (the 1B w2): the tile kernel with K split over workgroups; its
-                # combine launch IS the residual add + RMSNorm launch (md_linear_fused_split_add_rmsnorm)
-                return ops.fused_split_linear_add_rmsnorm(inp, pk, x, norm.weight, norm.eps, lin.bias, self.workspace)
-            how = choose(M, w.shape[0], K, False, w.dtype == torch.int8, pk is not None, "resid")
-            if how == "block" and ops.linear_block_supported(M, w.shape[0], K) and inp.stride(-1) == 1:
-                # 129..256 rows: the block-tile GEMM, same combine launch (residual add + RMSNorm)
-                return ops.linear_block_add_rmsnorm(inp, pk, x, norm.weight, norm.eps, lin.bias, self.workspace)
-            if (how in ("skinny", "block")
-                    and ops.linear_add_rmsnorm_supported(M, w.shape[0], K)):
-                return ops.linear_add_rmsnorm(inp, pk if pk is not None else w, x, norm.weight, norm.eps, lin.bias,
-                                              getattr(lin, "scales", None), self.workspace)
-        return self._reduce_add_norm(self._linear(inp, lin), x, norm, group)
+        if plan.add_norm and plan.how == "split":         # md_linear_fused_split_add_rmsnorm
+            return ops.fused_split_linear_add_rmsnorm(inp, pk, x, norm.weight, norm.eps, lin.bias, self.workspace)
+        if plan.add_norm and plan.how == "block":         # 129..256 rows: the block-tile GEMM, same combine launch
+            return ops.linear_block_add_rmsnorm(inp, pk, x, norm.weight, norm.eps, lin.bias, self.workspace)
+        if plan.add_norm:                                 # the weight-streaming kernel (md_linear_add_rmsnorm)
+            return ops.linear_add_rmsnorm(inp, pk if pk is not None else w, x, norm.weight, norm.eps, lin.bias,
+                                          getattr(lin, "scales", None), self.workspace)
+        return self._reduce_add_norm(self._linear(inp, lin), x, norm)
 
-    def _reduce_add_norm(self, partial, x, norm, group):
+    def _reduce_add_norm(self, partial, x, norm):
         """all-reduce of a sub-layer's partial output (C1), residual add, RMSNorm for the next sub-layer:
         (h, y) = (x + sum_ranks(partial), rmsnorm(h) * w).  With the xGMI all-reduce attached (tp.apply_tp,
         MAGICDEC_ONESHOT_AR=1) and a decode-sized message this is ONE launch (md_allreduce_add_rmsnorm); otherwise
         the collective (RCCL) followed by the fused add + norm kernel."""
-        if group is not None:
+        if self.process_group is not None:
             ar = getattr(self, "_oneshot", None)
             if ar is not None and ar.fits_fused(partial, norm.weight) and x.is_contiguous():
                 return ar.all_reduce_add_rmsnorm(partial, x, norm.weight, norm.eps)
-            partial = self._reduce(partial, group)
+            partial = self._reduce(partial, self.process_group)
         return ops.add_rmsnorm(x, partial, norm.weight, norm.eps)
 
     def _qkv(self, layer, y2d):
         c = self.config
-        att = layer.attention
-        qkv = self._linear(y2d, att.wqkv)                              # [rows, (H+2KH)*D]
+        qkv = self._linear(y2d, layer.attention.wqkv)                  # [rows, (H+2KH)*D]
         H, KH, D = c.n_head, c.n_local_heads, c.head_dim
-        rows = qkv.shape[0]
         q = qkv[:, :H * D].unflatten(1, (H, D))
         k = qkv[:, H * D:(H + KH) * D].unflatten(1, (KH, D))
         v = qkv[:, (H + KH) * D:].unflatten(1, (KH, D))
-        return q, k, v, rows
+        return q, k, v
 
     def _run(self, idx, attn_fn):
         """embed -> L x (norm, attention, +res, norm, mlp, +res) -> norm -> head -> argmax.
@@ -676,14 +662,13 @@ class Transformer(nn.Module):
         y = ops.rmsnorm(x, layers[0].attention_norm.weight, layers[0].attention_norm.eps)
         for i, layer in enumerate(layers):
             o = attn_fn(i, layer, y, n)
-            x, y = self._proj_add_norm(o.view(o.shape[0], -1), layer.attention.wo, x, layer.ffn_norm,
-                                       layer.attention.process_group)
+            x, y = self._proj_add_norm(o.view(o.shape[0], -1), layer.attention.wo, x, layer.ffn_norm)
             act = self._linear(y, None, swiglu_w13=(self._w13[i], self._s13[i]))
             nxt = layers[i + 1].attention_norm if i + 1 < len(layers) else self.norm
-            x, y = self._proj_add_norm(act, layer.feed_forward.w2, x, nxt, layer.feed_forward.process_group)
+            x, y = self._proj_add_norm(act, layer.feed_forward.w2, x, nxt)
         if self.skip_head:
             return None
-        logits = self._linear(y, self.output)                         # [rows, vocab / tp]; materialises a deferred norm
+        logits = self._linear(y, self.output)                         # [rows, vocab / tp]
         self._last_logits = logits
         if self.sampler is not None:                                  # Engine/sampling.py: draw instead of argmax
             return self.sampler.head(logits, self.sample_role, idx, B, n)
@@ -726,8 +711,9 @@ class Transformer(nn.Module):
             # consecutive rows (what every back-end passes: qo_indptr = arange * n); anything else takes rope_append, which
             # honours qo_indptr
             uniform_rows = yin.shape[0] == (qo_indptr.numel() - 1) * n
-            if (not need_calib and uniform_rows and self._fused_here(yin, att.wqkv.weight, "qkv", pro is not None)
-                    and c.head_dim in (64, 128)):
+            plan = self._plan("wqkv", att.wqkv.weight, yin.shape[0], pro is not None,
+                              guards=yin.is_cuda and uniform_rows and not need_calib)
+            if plan.how == "fused_qkv":
                 # (deferred RMSNorm +) wqkv + bias + RoPE + paged append (both caches of a self-speculation verify):
                 # ONE launch
                 q_rot = ops.fused_qkv_rope_append(
@@ -738,7 +724,7 @@ class Transformer(nn.Module):
             else:
                 if pro is not None:
                     y = pro.materialize()
-                q, k, v, _ = self._qkv(layer, y)
+                q, k, v = self._qkv(layer, y)
                 if need_calib:
                     if self.kv_scale_override is not None:
                         kvc.k_scale.copy_(self.kv_scale_override[i][0])
@@ -791,7 +777,7 @@ class Transformer(nn.Module):
         def fn(i, layer, y, n):
             if isinstance(y, ops.DeferredNorm):
                 y = y.materialize()
-            q, k, v, _ = self._qkv(layer, y)
+            q, k, v = self._qkv(layer, y)
             cache = getattr(layer.attention.kv_cache, which)
             ppr = cache.shape[0] // B
             overflow = ctx + n > kv_len

@@ -1327,6 +1327,264 @@ def test_gemm_policy_encodes_the_measured_ab_table():
     assert c(64, 3080, 2048, "plain") == "lib" and c(300, 768, 2048, "qkv") == "lib"
 
 
+def _shard_model(shapes, head_dim, n_layer=1, int8=False, tp=False, rows=None):
+    """A Transformer whose linears have exactly `shapes` (role -> (N, K); w13 = w1|w3), e.g. one rank's shards of a
+    tensor-parallel model.  Uninitialised weights: for tests of the dispatch and of the bookkeeping, which read shapes and
+    dtypes only."""
+    import torch.nn as nn
+    from magicdec_amd.Engine import model_core
+    from magicdec_amd.Engine.quantize import WeightOnlyInt8Linear
+    H = shapes["wo"][1] // head_dim
+    KH = (shapes["wqkv"][0] - H * head_dim) // (2 * head_dim)
+    with torch.device("meta"):
+        m = model_core.Transformer(model_core.ModelArgs(n_layer=n_layer, n_head=H, n_local_heads=KH, dim=H * head_dim,
+                                                        vocab_size=64, rope_base=500000.0))
+
+    def lin(N, K):
+        if int8:
+            return WeightOnlyInt8Linear(K, N)
+        l = nn.Linear(K, N, bias=False, device="meta")
+        l.weight = nn.Parameter(torch.empty((N, K), dtype=torch.bfloat16), requires_grad=False)
+        return l
+    for b in m.layers:
+        b.attention.wqkv, b.attention.wo = lin(*shapes["wqkv"]), lin(*shapes["wo"])
+        N13, K13 = shapes["w13"]
+        b.feed_forward.w1, b.feed_forward.w3 = lin(N13 // 2, K13), lin(N13 // 2, K13)
+        b.feed_forward.w2 = lin(*shapes["w2"])
+    m.output = lin(*shapes["head"])
+    if tp:
+        grp = object()              # a stand-in: nothing talks to torch.distributed unless it is initialised
+        m.process_group = grp
+        for b in m.layers:
+            b.attention.process_group = b.feed_forward.process_group = grp
+    m.setup_caches(num_pages=2, decode_rows=rows)
+    return m
+
+
+_ROLES = ("wqkv", "wo", "w13", "w2", "head")
+_SHAPES_1B = dict(wqkv=(3072, 2048), wo=(2048, 2048), w13=(16384, 2048), w2=(2048, 8192), head=(128256, 2048))
+_SHAPES_8B = dict(wqkv=(6144, 4096), wo=(4096, 4096), w13=(28672, 4096), w2=(4096, 14336), head=(128256, 4096))
+_SHAPES_8B_TP8 = dict(wqkv=(768, 4096), wo=(4096, 512), w13=(3584, 4096), w2=(4096, 1792), head=(16032, 4096))
+_SHAPES_70B_TP8 = dict(wqkv=(1280, 8192), wo=(8192, 1024), w13=(7168, 8192), w2=(8192, 3584), head=(16032, 8192))
+_SHAPES_1B_TP4 = dict(wqkv=(768, 2048), wo=(2048, 512), w13=(4096, 2048), w2=(2048, 2048), head=(32064, 2048))
+
+
+def _policy_overridden():
+    from magicdec_amd.Engine import gemm_policy as g
+    return (g.mode() != "auto" or g.fused_mode() != "auto" or g.block_mode() != "auto"
+            or g.packed_copies_mode() != "auto"
+            or any(os.environ.get(v, d) != d for v, d in (("MAGICDEC_SPLIT", "auto"), ("MAGICDEC_WO256", "1"),
+                                                          ("MAGICDEC_SHARD70B", "1"), ("MAGICDEC_SKINNY_NORM", "auto"),
+                                                          ("MAGICDEC_DEEP_SWIGLU_L2", "150e6"),
+                                                          ("MAGICDEC_KEEP_ROWMAJOR", "0"))))
+
+
+def test_step_plan_walk_pins_which_kernel_serves_which_weight():
+    """Transformer._step_hows walks the linears of a step in execution order through model_core.plan_linear and answers,
+    per weight, which implementations a step of M rows runs it on; _pack_weights and release_rowmajor decide from it which
+    weights get a streaming-layout copy and which row-major tensors are freed after prefill.  Pinned here for the
+    production shapes: the values are those of the per-role predictor this walk replaced (recorded from it before the
+    change, over 16 200 cases of model x TP degree x row set x weight type x policy switch, all identical); in that
+    table the fused qkv + rope + append launch is spelled "fused" like the plain tile kernel."""
+    if _policy_overridden():
+        pytest.skip("policy overridden by the environment")
+    table = [     # shapes, head_dim, tp, int8, rows, {M: wqkv wo w13 w2 head}, packed, released after prefill
+        ("1B draft", _SHAPES_1B, 64, False, False, (64, 128),
+         {64: "fused fused fused split skinny", 128: "fused fused fused split skinny"},
+         "head w13 w2 wo wqkv", "head w13 w2 wo wqkv"),
+        ("8B target", _SHAPES_8B, 128, False, False, (64, 256),
+         {64: "lib fused skinny skinny skinny", 256: "lib fused block block block"},
+         "head w13 w2 wo", "head w13 w2 wo"),
+        ("8B with a two-token step", _SHAPES_8B, 128, False, False, (64, 128, 256),
+         {64: "lib fused skinny skinny skinny", 128: "fused lib block skinny skinny", 256: "lib fused block block block"},
+         "head w13 w2 wo wqkv", "head w13 w2"),
+        ("8B, one TP-8 rank", _SHAPES_8B_TP8, 128, True, False, (64, 256),
+         {64: "fused fused fused fused skinny", 256: "fused fused fused lib lib"},
+         "head w13 w2 wo wqkv", "w13 wo wqkv"),
+        ("70B, one TP-8 rank", _SHAPES_70B_TP8, 128, True, False, (32, 128),
+         {32: "lib fused skinny fused skinny", 128: "fused fused skinny fused skinny"},
+         "head w13 w2 wo wqkv", "head w13 w2 wo"),
+        ("1B draft, one TP-4 rank", _SHAPES_1B_TP4, 64, True, False, (32, 64),
+         {32: "fused fused fused fused skinny", 64: "fused fused fused fused skinny"},
+         "head w13 w2 wo wqkv", "head w13 w2 wo wqkv"),
+        ("8B int8", _SHAPES_8B, 128, False, True, (64, 256),
+         {64: "skinny skinny skinny skinny skinny", 256: "skinny skinny skinny skinny skinny"},
+         "head w13 w2 wo wqkv", ""),
+    ]
+    from magicdec_amd import ops
+
+    class NoCopy:                       # the walk and the bookkeeping read no weight values: skip the permutes
+        def __init__(self, weight, swiglu=False):
+            self.data = torch.empty(0, dtype=weight.dtype)
+    real, ops.PackedWeight = ops.PackedWeight, NoCopy
+    try:
+        for label, shapes, head_dim, tp, int8, rows, hows, packed, released in table:
+            m = _shard_model(shapes, head_dim, int8=int8, tp=tp, rows=rows)
+            lay = m.layers[0]
+            ws = dict(wqkv=lay.attention.wqkv.weight, wo=lay.attention.wo.weight, w13=m._w13[0],
+                      w2=lay.feed_forward.w2.weight, head=m.output.weight)
+            for M, want in hows.items():
+                got = m._step_hows(M)
+                got = " ".join("|".join(sorted({"fused" if h == "fused_qkv" else h for h in got[r]})) for r in _ROLES)
+                assert got == want, (label, M, got, want)
+            m._pack_weights(force=True)
+            assert " ".join(sorted(r for r, w in ws.items() if id(w) in m._packed)) == packed, label
+            m.release_rowmajor()
+            assert " ".join(sorted(r for r, w in ws.items() if id(w) in m._released)) == released, label
+    finally:
+        ops.PackedWeight = real
+
+
+def test_every_linear_of_a_step_runs_what_the_plan_answers(monkeypatch):
+    """Execution follows the plan: one decode / verify step with every GEMM wrapper of magicdec_amd.ops (and the library
+    GEMM) replaced by a recorder, on activations that answer `is_cuda`.  Each site must call exactly the wrapper
+    model_core.plan_linear names for it, hand a deferred norm on only where the plan says the kernel absorbs it (and
+    materialise it otherwise), and stay inside what Transformer._step_hows predicted for that weight -- so that a step
+    after release_rowmajor() never needs a freed row-major tensor."""
+    if _policy_overridden():
+        pytest.skip("policy overridden by the environment")
+    from magicdec_amd import ops
+    from magicdec_amd.Engine import model_core
+
+    class OnGpu(torch.Tensor):
+        is_cuda = property(lambda self: True)
+
+    def act(*shape, dtype=torch.bfloat16):
+        return torch.zeros(shape, dtype=dtype).as_subclass(OnGpu)
+
+    class NoCopy:
+        def __init__(self, weight, swiglu=False):
+            self.N, self.K, self.swiglu, self.dtype = weight.shape[0], weight.shape[1], swiglu, weight.dtype
+            self.data = torch.empty(0, dtype=weight.dtype)
+
+        def unpack(self):
+            return torch.empty((self.N, self.K), dtype=self.dtype)
+    calls, norms = [], []
+
+    def n_of(weight):
+        return weight.N if isinstance(weight, NoCopy) else weight.shape[0]
+
+    def gemm(name, weight, x, pro=None, swiglu=False):
+        calls.append((name, id(weight), pro is not None))
+        return act(x.shape[0], n_of(weight) // (2 if swiglu else 1))
+
+    def fused_linear(x, weight, bias=None, swiglu=False, resid=None, out=None, want_ssq=False, pro=None):
+        y = gemm("fused_linear+resid" if resid is not None else "fused_linear", weight, x, pro, swiglu)
+        return (y, act(x.shape[0], weight.N // 32, dtype=torch.float32)) if want_ssq else y
+
+    def fused_qkv(x, weight, bias, H, KH, D, n, *a, pro=None, **kw):
+        gemm("fused_qkv_rope_append", weight, x, pro)
+        return act(x.shape[0], H, D)
+
+    def add_norm(name):
+        def f(x, weight, resid, norm_weight, eps, *a, **kw):
+            y = gemm(name, weight, x)
+            return y, y
+        return f
+
+    def rmsnorm(x, w, eps):
+        norms.append(tuple(x.shape))
+        return act(*x.shape)
+
+    class Lib:
+        @staticmethod
+        def linear(x, w, bias=None):
+            return gemm("F.linear", w, x)
+    monkeypatch.setattr(ops, "PackedWeight", NoCopy)
+    monkeypatch.setattr(ops, "fused_linear", fused_linear)
+    monkeypatch.setattr(ops, "fused_qkv_rope_append", fused_qkv)
+    monkeypatch.setattr(ops, "linear", lambda x, weight, bias=None, scales=None, swiglu=False, workspace=None, out=None,
+                        pro=None: gemm("linear", weight, x, pro, swiglu))
+    monkeypatch.setattr(ops, "linear_block", lambda x, weight, bias=None, swiglu=False, workspace=None, out=None:
+                        gemm("linear_block", weight, x, None, swiglu))
+    for name in ("fused_split_linear_add_rmsnorm", "linear_block_add_rmsnorm", "linear_add_rmsnorm"):
+        monkeypatch.setattr(ops, name, add_norm(name))
+    monkeypatch.setattr(ops, "rmsnorm", rmsnorm)
+    monkeypatch.setattr(ops, "add_rmsnorm", lambda x, r, w, eps: (act(*x.shape), act(*x.shape)))
+    monkeypatch.setattr(ops, "silu_mul", lambda a, b: act(*a.shape))
+    monkeypatch.setattr(ops, "rope_append", lambda q, *a, **kw: act(*q.shape))
+    monkeypatch.setattr(ops, "paged_attention", lambda q, *a, **kw: act(*q.shape))
+    monkeypatch.setattr(ops, "argmax", lambda logits, *a, **kw: torch.zeros(logits.shape[0], dtype=torch.long))
+    monkeypatch.setattr(model_core, "F", Lib)
+    wrapper = {"fused": "fused_linear", "block": "linear_block", "skinny": "linear", "lib": "F.linear"}
+
+    def run(m, B, n, uniform=True):
+        """One step of B x n rows; returns [(role, wrapper called, deferred norm handed on)] and what the plan says."""
+        M, dim = B * n, m.layers[0].attention.wo.weight.shape[0]
+        monkeypatch.setattr(m.tok_embeddings, "forward", lambda idx: act(B, n, dim))
+        role = {}
+        chain = []
+        for i, b in enumerate(m.layers):
+            chain += [("wqkv", "wqkv", b.attention.wqkv.weight), ("wo", "proj", b.attention.wo.weight),
+                      ("w13", "w13", m._w13[i]), ("w2", "proj", b.feed_forward.w2.weight)]
+        chain.append(("head", "plain", m.output.weight))
+        want, deferred, materialised = [], False, 1              # (the norm in front of layer 0)
+        for r, site, w in chain:
+            role[id(w)] = role[id(m._packed.get(id(w)))] = r
+            plan = m._plan(site, w, M, deferred, guards=uniform or site != "wqkv")
+            if plan.how == "fused_qkv":
+                name = "fused_qkv_rope_append"
+            elif plan.defers_norm:
+                name = "fused_linear+resid"
+            elif plan.add_norm:
+                name = {"split": "fused_split_linear_add_rmsnorm", "block": "linear_block_add_rmsnorm",
+                        "skinny": "linear_add_rmsnorm"}[plan.how]
+            else:
+                name = wrapper[plan.how]
+            want.append((r, name, deferred and plan.absorbs_norm))
+            materialised += deferred and not plan.absorbs_norm
+            assert plan.how in m._step_hows(M)[r] or not uniform, (r, M, plan)
+            deferred = plan.defers_norm
+        calls.clear(), norms.clear()
+        qo = torch.arange(B + 1, dtype=torch.int32) * n if uniform else torch.arange(B // 2 + 1, dtype=torch.int32) * 2 * n
+        tab = model_core.PageTable(torch.zeros(B, dtype=torch.int32), torch.arange(B + 1, dtype=torch.int32),
+                                   torch.ones(B, dtype=torch.int32), 1)
+        m.forward(torch.zeros(B, n, dtype=torch.long), torch.zeros(B, dtype=torch.int32), qo, tab)
+        got = [(role[w], name, pro) for name, w, pro in calls]
+        assert got == want, (M, got, want)
+        assert len(norms) == materialised, (M, norms, materialised)
+        return got
+
+    # the 1B draft's layers at 64 rows and at the 128 rows of its two-token step: everything on the tile kernels, the norm
+    # behind wo deferred into the w1|w3 launch
+    m = _shard_model(_SHAPES_1B, 64, n_layer=2, rows=(64, 128))
+    m._pack_weights(force=True)
+    got = run(m, 64, 1)
+    assert got[:4] == [("wqkv", "fused_qkv_rope_append", False), ("wo", "fused_linear+resid", False),
+                       ("w13", "fused_linear", True), ("w2", "fused_split_linear_add_rmsnorm", False)]
+    m.release_rowmajor()
+    assert len(m._released) == 9
+    run(m, 64, 1), run(m, 64, 2)
+    assert not m._warned_transient                  # no step needed a released row-major tensor
+    # rows not owned uniformly by the requests: no fused qkv epilogue, the projection runs through `_linear`
+    m.restore_rowmajor()
+    assert run(m, 64, 1, uniform=False)[0][:2] == ("wqkv", "fused_linear")
+    # the 68m model's layers: w2 takes the residual epilogue too, so layer 1's wqkv launch absorbs the norm in front of it
+    m = _shard_model(dict(wqkv=(2304, 768), wo=(768, 768), w13=(6144, 768), w2=(768, 3072), head=(32000, 768)), 64,
+                     n_layer=2, rows=(64,))
+    m._pack_weights(force=True)
+    got = run(m, 64, 1)
+    assert got[3] == ("w2", "fused_linear+resid", False) and got[4] == ("wqkv", "fused_qkv_rope_append", True)
+    # an 8B target layer at 64 and 256 rows: library wqkv, fused wo (norm deferred into the streaming / block kernels)
+    m = _shard_model(_SHAPES_8B, 128, n_layer=2, rows=(64, 256))
+    m._pack_weights(force=True)
+    m.release_rowmajor()
+    got = run(m, 64, 1)
+    assert got[:4] == [("wqkv", "F.linear", False), ("wo", "fused_linear+resid", False), ("w13", "linear", True),
+                       ("w2", "linear_add_rmsnorm", False)]
+    got = run(m, 64, 4)
+    assert got[4:] == [("wqkv", "F.linear", False), ("wo", "fused_linear+resid", False), ("w13", "linear_block", False),
+                       ("w2", "linear_block_add_rmsnorm", False), ("head", "linear_block", False)]
+    assert not m._warned_transient
+    # the same weights as one rank of a tensor-parallel group: no residual / add + norm epilogue, the plain kernels and
+    # the collective's add + norm behind them
+    m = _shard_model(_SHAPES_8B_TP8, 128, tp=True, rows=(64, 256))
+    m._pack_weights(force=True)
+    monkeypatch.setattr(m, "_reduce", lambda y, group: y)
+    monkeypatch.setattr(m, "_argmax", lambda logits: torch.zeros(logits.shape[0], dtype=torch.long))
+    assert [c[1] for c in run(m, 64, 1)] == ["fused_qkv_rope_append", "fused_linear", "fused_linear", "fused_linear", "linear"]
+
+
 def test_iteration_hook_runs_after_the_body_and_before_the_host_read():
     """LoopState.before_host_read: device-side statistics are queued behind the accept kernel and in front of the
     iteration's one host read (bench.py counts its tokens there)."""
