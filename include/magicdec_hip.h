@@ -441,7 +441,9 @@ int md_accept_rollback(int64_t* tokens_buffer, const int64_t* target_tokens, int
  *              accept d iff u_j q~_j(d) < p~_j(d) (u_j: purpose ACCEPT, step j).  At the first rejection jr the
  *              token is a Gumbel-max draw over log max(p~_jr - q~_jr, 0) (purpose RESIDUAL, step jr; if that is 0
  *              everywhere after rounding: a draw from p~_jr without d); if every draft is accepted, the bonus is a
- *              draw from p~_gamma (purpose BONUS, step gamma).  Output target_tokens [B, gamma+1] int64: d_j for
+ *              draw from p~_gamma (purpose BONUS, step gamma).  A draft token outside [0, vocab) is a rejection at
+ *              its position (no row is indexed with it; the residual is drawn as for any rejection and its fallback
+ *              excludes nothing).  Output target_tokens [B, gamma+1] int64: d_j for
  *              j < jr, the corrected token at jr, -1 after it -- md_accept_rollback, unchanged, then yields the
  *              accept count and the corrected token (the argument is above the kernel in csrc/sample.hip).
  * counters: int32 [4] on the device: [0] iteration, [1] draft step j, [2] ticket (0 between launches), [3] unused.

@@ -779,6 +779,14 @@ def _sample_args(logits, temperature, top_p):
         raise ValueError(f"sampling needs temperature > 0 and 0 < top_p <= 1, got {temperature}, {top_p}")
 
 
+def _sample_state(counters, **int64_tensors):
+    if counters.dtype != torch.int32 or counters.numel() < 4 or not counters.is_contiguous():
+        raise ValueError("sampling: counters must be a contiguous int32 [4] tensor")
+    for name, t in int64_tensors.items():
+        if t is not None and t.dtype != torch.int64:
+            raise ValueError(f"sampling: {name} must be int64, got {t.dtype}")
+
+
 def sample_rows(logits, n, temperature, top_p, seed, purpose, counters, advance, row_sel=None, ring=None,
                 ring_stats=None, out=None):
     """Tempered top-p Gumbel-max draw of ONE row per request from logits [B*n, vocab] bf16 (row row_sel[b]-1 of the
@@ -792,12 +800,17 @@ def sample_rows(logits, n, temperature, top_p, seed, purpose, counters, advance,
         raise ValueError(f"sample_rows: {rows} rows are not B x n = {n}")
     B = rows // n
     gamma = 0
+    if (ring is None) != (ring_stats is None):
+        raise ValueError("sample_rows: ring and ring_stats go together")
+    _sample_state(counters, ring_stats=ring_stats, out=out)
     if ring is not None:
         _gpu(ring, ring_stats)
         if ring.shape[0] != B or ring.shape[2] != vocab or not ring.is_contiguous() or ring.dtype != torch.bfloat16:
             raise ValueError(f"sample_rows: the draft ring must be a contiguous bf16 [B={B}, gamma, vocab={vocab}] tensor "
                              f"(draft and target vocabularies must be equal); got {tuple(ring.shape)}")
         gamma = ring.shape[1]
+        if gamma < 1:           # an empty ring has a null data pointer: the library would take it for "no ring"
+            raise ValueError("sample_rows: a draft ring needs gamma >= 1")
         if tuple(ring_stats.shape) != (B, gamma, STATS_WORDS) or not ring_stats.is_contiguous():
             raise ValueError("sample_rows: ring_stats must be a contiguous [B, gamma, 2] int64 tensor")
     if row_sel is not None:
@@ -806,6 +819,8 @@ def sample_rows(logits, n, temperature, top_p, seed, purpose, counters, advance,
             raise ValueError("sample_rows: row_sel must be a contiguous int64 [B] tensor")
     if out is None:
         out = torch.empty((B, n), dtype=torch.int64, device=logits.device)
+    elif tuple(out.shape) != (B, n) or not out.is_contiguous():
+        raise ValueError(f"sample_rows: out must be a contiguous [B={B}, n={n}] tensor")
     check(_lib.load().md_sample_rows(_p(logits), logits.stride(0), B, n, vocab, float(temperature), float(top_p),
                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(purpose), _p(row_sel), _p(counters),
                                      int(advance), _p(ring), _p(ring_stats), gamma, _p(out), _stream()),
@@ -817,20 +832,29 @@ def spec_verify_sample(logits, tokens_buffer, ring, ring_stats, target_stats, co
                        out=None):
     """Speculative-sampling verify: target logits [B*(gamma+1), vocab] bf16, the draft ring / stats of this iteration and
     tokens_buffer [B, gamma+1] -> target_tokens [B, gamma+1] int64 in the encoding ops.accept_rollback consumes
-    unchanged.  target_stats: [B*(gamma+1), 2] int64 workspace (holds the target rows' stats afterwards)."""
-    _gpu(logits, tokens_buffer, ring, ring_stats, target_stats, counters)
+    unchanged.  target_stats: [B*(gamma+1), 2] int64 workspace (holds the target rows' stats afterwards).  A draft
+    token outside [0, vocab) is rejected at its position.  tokens_buffer may be a non-contiguous view (it is copied)."""
+    _gpu(logits, tokens_buffer, ring, ring_stats, target_stats, counters, out)
     _sample_args(logits, temperature, top_p)
+    _sample_state(counters, tokens_buffer=tokens_buffer, ring_stats=ring_stats, target_stats=target_stats, out=out)
+    if tokens_buffer.dim() != 2:
+        raise ValueError("spec_verify_sample: tokens_buffer must be [B, gamma+1]")
     B, G1 = tokens_buffer.shape
     rows, vocab = logits.shape
-    if rows != B * G1 or tuple(ring.shape) != (B, G1 - 1, vocab) or ring.dtype != torch.bfloat16:
+    if (rows != B * G1 or tuple(ring.shape) != (B, G1 - 1, vocab) or ring.dtype != torch.bfloat16
+            or not ring.is_contiguous()):
         raise ValueError(f"spec_verify_sample: logits {tuple(logits.shape)}, ring {tuple(ring.shape)} and tokens_buffer "
                          f"{tuple(tokens_buffer.shape)} disagree (draft and target vocabularies must be equal)")
-    if tuple(target_stats.shape) != (rows, STATS_WORDS) or tuple(ring_stats.shape) != (B, G1 - 1, STATS_WORDS):
-        raise ValueError("spec_verify_sample: stats tensors must be [rows, 2] / [B, gamma, 2] int64")
+    if (tuple(target_stats.shape) != (rows, STATS_WORDS) or tuple(ring_stats.shape) != (B, G1 - 1, STATS_WORDS)
+            or not target_stats.is_contiguous() or not ring_stats.is_contiguous()):
+        raise ValueError("spec_verify_sample: stats tensors must be contiguous [rows, 2] / [B, gamma, 2] int64")
     if out is None:
         out = torch.empty((B, G1), dtype=torch.int64, device=logits.device)
+    elif tuple(out.shape) != (B, G1) or not out.is_contiguous():
+        raise ValueError(f"spec_verify_sample: out must be a contiguous [B={B}, gamma+1={G1}] tensor")
+    tb = tokens_buffer.contiguous()         # a named local: a temporary copy stays alive until the launch is queued
     check(_lib.load().md_spec_verify_sample(_p(logits), logits.stride(0), B, G1 - 1, vocab, float(temperature),
-                                            float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(tokens_buffer.contiguous()),
+                                            float(top_p), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(tb),
                                             _p(ring), _p(ring_stats), _p(target_stats), _p(counters), _p(out),
                                             _stream()), "md_spec_verify_sample")
     return out

@@ -3,7 +3,8 @@
 The hand-picked cases of test_gpu_ops.py / test_gpu_gemm.py / test_gpu_fused.py cover the shapes the Engine passes and the
 edges we thought of; this file draws shapes nobody thought of.  Every case is derived from a fixed seed (the sweep is
 deterministic and a failure names its seed); MAGICDEC_FUZZ_CASES=<n> widens every sweep to n cases (default below: the whole
-file runs in well under a minute; one wide run: profiles/r06_fuzz_11000_cases.txt).
+file runs in well under a minute -- the sampling family's default cases, CPU-bound restatement included, take about 2 s of
+it; one wide run: profiles/r06_fuzz_11000_cases.txt, and profiles/sampling_fuzz_wide.txt for the sampling family).
 
 * paged attention: request count, ragged query-row counts (0 rows included), head grouping g in {1,2,3,4,5,7,8}, D, context
   lengths from 0 to a few thousand rows, page size in {32, 64, 128}, scattered page tables, NHD / HND pages, bf16 / fp8
@@ -14,7 +15,13 @@ file runs in well under a minute; one wide run: profiles/r06_fuzz_11000_cases.tx
 * argmax with planted ties: BIT-EXACT, lowest index;
 * SnapKV select on integer-valued inputs (scores exact in any summation order): scores, indices, gathered rows BIT-EXACT;
 * StreamingLLM eviction + re-rotation chunk by chunk, and the fused accept / rollback kernel on random batches: BIT-EXACT
-  against the oracle functions that tests/golden pins to the real reference.
+  against the oracle functions that tests/golden pins to the real reference;
+* sampling (K11): whole draft / verify / accept iterations -- B 1..48 (sometimes > 512 on a small vocabulary), gamma 1..5,
+  V in {50, 1001, 2048, 16384, 32003, 128256}, T log-uniform in [0.2, 3], top_p 1 or in [0.3, 0.99], logit scale, draft
+  distance sigma (0 = bit-equal rows), planted tie groups / -inf spans / peaked tokens, a one- or two-token first draft step
+  with a random row_sel, a random starting iteration, dense or padded logits views, real end-of-text ids: the stats of
+  every row, the ring BIT-EXACT, draft tokens and target_tokens of a bounded subset of requests inside the admissible set
+  of tests/sampling_ref.py, the accept state BIT-EXACT against cpu_ops.accept_rollback.
 """
 import os
 import random
@@ -23,6 +30,7 @@ import pytest
 import torch
 
 from oracle import flashinfer_ref as fr
+from tests import sampling_cases as sc
 from tests.conftest import parity_report
 from tests.parity_util import check_attention, dense_attention_f64
 from tests.test_gpu_ops import _ulp_close, bits, make_paged
@@ -495,3 +503,24 @@ def test_fuzz_fused_qkv_rope_append_and_tile_shapes(ops, seed):
     M, N, K3 = r.choice([1, 33, 64, 100, 128, 256]), 64 * r.randint(1, 40), 128 * r.randint(1, 24)
     if ops.fused_linear_supported(M, N, K3):
         tf.test_fused_2x2_tiles_bit_identical_to_1x1(ops, M, N, K3)
+
+
+# ----------------------------------------------------------------------------------------- sampling (K11)
+@pytest.mark.parametrize("seed", cases(sc.FUZZ_DEFAULT))
+def test_fuzz_sampling_vs_restatement(ops, seed):
+    """One random draft / verify / accept iteration per seed (tests/sampling_cases.py::fuzz_case) against the
+    admissible-outcome oracle and cpu_ops.accept_rollback; the restated work is bounded per case (4 requests on a large
+    vocabulary, 10 on a small one; the stats of every row are always checked)."""
+    from tests import test_gpu_sampling as tgs
+    c = sc.fuzz_case(seed)
+    tag = (f"seed {seed}: V{c['V']} B{c['B']} gamma{c['G']} T{c['T']:.3f} top_p{c['top_p']:.3f} n0={c['dl'][0].shape[1]} "
+           f"it{c['it']} pad={c['pad']} eot={c['eot']}")
+    try:
+        o = tgs._run_iteration(c)
+        assert o["ctr"] == [c["it"] + 1, 0, 0, 0]
+        n, amb = sc.check_iteration(c, o["ring"], o["rst"], o["tst"], o["drafts"], o["tt"], o["tokens"])
+        tgs._accept_kernel_equals_cpu(o["tokens"], o["tt"], c["G"], *c["eot"])
+    except AssertionError as e:
+        raise AssertionError(f"{tag}: {e}") from e
+    parity_report(f"[fuzz-sampling] {tag}: stats of {c['B'] * (2 * c['G'] + 1)} rows, {n} requests restated, {amb} with "
+                  f"more than one admissible outcome, 0 tokens outside the admissible set")
