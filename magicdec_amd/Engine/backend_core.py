@@ -15,6 +15,12 @@ What is different underneath:
   * the lm head runs only on the last prefill chunk (the reference computes and
     discards 128 x vocab logits per chunk);
   * `compile()` captures the decode step into a hipGraph (there is no Inductor).
+
+How the file reads: `_PagedState` is one page table (its three attributes on the back-end, the form it resets to);
+`_BackendBase` holds what the four back-ends share -- `_alloc_state` / `clear_kv`, the chunked `_paged_prefill`, and
+`_step`, the body of every inference / verify / speculate: it alone advances lengths and hands Engine/graph.py the names
+of the attributes the step reads.  The four classes keep their own `setup_caches` (the reference's attribute names
+differ) and, around their `_step` call, whatever the reference does for that method only.
 """
 from __future__ import annotations
 
@@ -50,10 +56,16 @@ def _pages_per_request(max_batch_size, max_seq_length, page_size=PAGE_SIZE):
 
 
 class _PagedState:
-    """One paged cache's bookkeeping under a name prefix ('' or 'draft_') on the owning back-end."""
+    """One paged cache's bookkeeping under a name prefix ('' or 'draft_') on the owning back-end, and the form its table
+    starts from (at construction and at every reset()): empty with `indptr_stride` entries of the index vector per
+    request, or -- `full_table`, the SnapKV draft cache -- every page mapped from the start."""
 
-    def __init__(self, owner, prefix, ppr):
+    def __init__(self, owner, prefix, ppr, last_page_len_init=0, full_table=False, indptr_stride=1):
         self.o, self.p, self.ppr = owner, prefix, ppr
+        self.last_page_len_init, self.full_table, self.indptr_stride = last_page_len_init, full_table, indptr_stride
+        # the attributes a step that is passed table() reads (Engine/graph.py pins them)
+        self.names = tuple(prefix + n for n in ("paged_kv_indices", "paged_kv_indptr", "paged_kv_last_page_len"))
+        self.reset()
 
     def _get(self, name):
         return getattr(self.o, self.p + name)
@@ -61,19 +73,23 @@ class _PagedState:
     def _set(self, name, val):
         setattr(self.o, self.p + name, val)
 
-    def reset(self, last_page_len_init=0, full_table=False, indptr_stride=1):
+    # `state.last_page_len += n` updates the owner's tensor in place, `state.last_page_len = t` rebinds the attribute
+    last_page_len = property(lambda self: self._get("paged_kv_last_page_len"),
+                             lambda self, val: self._set("paged_kv_last_page_len", val))
+
+    def reset(self):
         o, B, dev = self.o, self.o.batch_size, self.o.device
         ppr = self.ppr
         self._set("num_pages_per_request", torch.zeros(B, dtype=torch.int32, device=dev))
         self.host_pages = 0
-        if full_table:   # SnapKV draft cache: all pages mapped from the start (backend.py:87-90)
+        if self.full_table:   # SnapKV draft cache: all pages mapped from the start (backend.py:87-90)
             self._set("paged_kv_indptr", torch.arange(B + 1, dtype=torch.int32, device=dev) * ppr)
             self._set("paged_kv_indices", torch.arange(B * ppr, dtype=torch.int32, device=dev))
             self.host_pages = ppr
         else:
-            self._set("paged_kv_indptr", torch.arange(B + 1, dtype=torch.int32, device=dev) * indptr_stride)
+            self._set("paged_kv_indptr", torch.arange(B + 1, dtype=torch.int32, device=dev) * self.indptr_stride)
             self._set("paged_kv_indices", torch.zeros(B * ppr, dtype=torch.int32, device=dev))
-        self._set("paged_kv_last_page_len", torch.full((B,), last_page_len_init, dtype=torch.int32, device=dev))
+        self.last_page_len = torch.full((B,), self.last_page_len_init, dtype=torch.int32, device=dev)
 
     def map_pages(self, n_pages, last_page_len):
         """Request b maps pages b*ppr .. b*ppr+n_pages-1; last page holds `last_page_len` rows
@@ -84,11 +100,27 @@ class _PagedState:
         base = torch.arange(B, dtype=torch.int32, device=dev).view(-1, 1) * self.ppr
         self._set("paged_kv_indices", (base + torch.arange(n_pages, dtype=torch.int32, device=dev).view(1, -1)).flatten())
         self._get("paged_kv_indptr").copy_(torch.arange(B + 1, dtype=torch.int32, device=dev) * n_pages)
-        self._set("paged_kv_last_page_len", torch.full((B,), last_page_len, dtype=torch.int32, device=dev))
+        self.last_page_len = torch.full((B,), last_page_len, dtype=torch.int32, device=dev)
 
     def table(self):
-        return PageTable(self._get("paged_kv_indices"), self._get("paged_kv_indptr"),
-                         self._get("paged_kv_last_page_len"), max(self.host_pages, 1))
+        return PageTable(self._get("paged_kv_indices"), self._get("paged_kv_indptr"), self.last_page_len,
+                         max(self.host_pages, 1))
+
+
+def _chunks(input_ids):
+    """The prefill walk: per chunk of CHUNK columns (ids, n, is_last, final).  `is_last` is the reference's flag -- a
+    chunk shorter than CHUNK was seen, and it sticks (backend.py:238-245); it is what triggers the SnapKV select and the
+    StreamingLLM rotation.  `final` is the walk's last chunk, the only one whose tokens anybody reads.  A prefix that is
+    a multiple of CHUNK has a final chunk and no is_last one."""
+    seq_len = input_ids.shape[1]
+    num_chunks = (seq_len + CHUNK - 1) // CHUNK
+    is_last = False
+    for i in range(num_chunks):
+        ids = input_ids[:, i * CHUNK:min((i + 1) * CHUNK, seq_len)]
+        n = ids.shape[1]
+        if n != CHUNK:
+            is_last = True
+        yield ids, n, is_last, i == num_chunks - 1
 
 
 class _BackendBase:
@@ -112,6 +144,30 @@ class _BackendBase:
         """The reference compiles with Inductor/Triton + CUDA graphs (Engine/SnapKV/backend.py:116-125); here the
         decode steps are captured into hipGraphs on first use (see Engine/graph.py)."""
         self._use_graphs = True
+
+    def _alloc_state(self, max_batch_size, pages_per_request):
+        """What every setup_caches() allocates: the length tensor, qo_indptr and the un-prefixed paged state `_t`.  An
+        engine with a second cache then makes its 'draft_' state `_d`, stating that table's initial form."""
+        self.batch_size, self.page_size = max_batch_size, PAGE_SIZE
+        self.cachelens = torch.zeros(max_batch_size, dtype=torch.int32, device=self.device)
+        self.qo_indptr = torch.arange(max_batch_size + 1, dtype=torch.int32, device=self.device)
+        self._t = _PagedState(self, "", pages_per_request)
+        self._d = None
+
+    @torch.no_grad()
+    def clear_kv(self):
+        for b in self.model.layers:
+            b.attention.kv_cache.kv_cache.zero_()
+            if self._d is not None:
+                b.attention.kv_cache.draft_cache.zero_()
+        self._reset_kv_calibration()
+        self.cachelens.zero_()
+        if getattr(self, "draft_cachelens", None) is not None:
+            self.draft_cachelens.zero_()
+        self.qo_indptr = torch.arange(self.batch_size + 1, dtype=torch.int32, device=self.device)
+        self._t.reset()
+        if self._d is not None:
+            self._d.reset()
 
     def _qo(self, n):
         return self.qo_indptr * n
@@ -140,11 +196,51 @@ class _BackendBase:
         for b in self.model.layers:
             b.attention.kv_cache.calibrated = False
 
-    def _run_step(self, key, fn, *tensors):
+    def _paged_prefill(self, input_ids, draft: _PagedState = None):
+        """Chunked prefill of the full-context cache `_t` (backend.py:232-268, backend_draft.py:176-209,
+        StreamingLLM/backend.py:190-211); with `draft`, the is_last chunk also runs the SnapKV select into that cache.
+        Returns (tokens of the final chunk, whether an is_last chunk ran)."""
+        tokens, is_last, done = None, False, 0
+        for i, (ids, n, is_last, final) in enumerate(_chunks(input_ids)):
+            self._t.map_pages(i + 1, n)                       # pre_encode
+            self.model.skip_head = not final
+            self.model.sample_role = "prefill"
+            tokens = self.model.prefill(ids, self.cachelens, self._qo(n), self._t.table(), is_last=is_last,
+                                        draft_tab=draft.table() if (draft is not None and is_last) else None,
+                                        ctx_len=done + n)
+            self.cachelens += n
+            done += n
+        self.model.skip_head = False
+        return tokens, is_last
+
+    def _step(self, kind, model_fn, lens_attr, state: _PagedState, tables, role, input_ids, cachelen_update=None,
+              benchmark=False):
+        """One decode step, as every public step method runs it: the rows are counted into `state`'s last page
+        (pre_decode / pre_verify / pre_spec), `model_fn(ids, lengths, qo_indptr * n, *tables)` runs -- as a replay of its
+        captured hipGraph after compile(), keyed by `kind` and pinning exactly the attributes it reads -- and the length
+        attribute `lens_attr` advances by n, or by `cachelen_update` after a two-token step, whose last-page length is
+        REBOUND to a new tensor like the reference's; benchmark=True undoes the updates (backend.py:140-143)."""
+        n = input_ids.shape[1]
+        state.last_page_len += n
+        self.model.sample_role = role
+        fn = lambda ids: model_fn(ids, getattr(self, lens_attr), self._qo(n), *(t.table() for t in tables))
         if self._use_graphs:
             from .graph import run_captured
-            return run_captured(self, key, fn, *tensors)
-        return fn(*tensors)
+            names = (lens_attr, "qo_indptr") + tuple(name for t in tables for name in t.names)
+            out = run_captured(self, (kind, n), names, fn, input_ids)
+        else:
+            out = fn(input_ids)
+        lens = getattr(self, lens_attr)
+        if cachelen_update is None:
+            lens += n
+        else:
+            cu = cachelen_update.to(torch.int32).flatten()
+            lens += cu
+            state.last_page_len = state.last_page_len - n + cu
+        if benchmark:
+            lens -= n
+            state.last_page_len -= n
+        return out
 
 
 # ======================================================================================= target (+ SnapKV self-spec)
@@ -168,21 +264,15 @@ class SnapKVTargetBackend(_BackendBase):
         reference's flashinfer wrappers are planned "NHD": Engine/SnapKV/backend.py:30); same results, longer
         contiguous runs for the verify step's stream (matters for fp8 rows of 128 bytes).  None = default_kv_layout()."""
         kv_layout = default_kv_layout() if kv_layout is None else kv_layout
-        self.max_length, self.batch_size = max_seq_length, max_batch_size
-        dev = self.device
-        self.page_size = PAGE_SIZE
+        self.max_length = max_seq_length
         self.max_num_pages, self.max_num_pages_per_request = _pages_per_request(max_batch_size, max_seq_length)
-        self.cachelens = torch.zeros(max_batch_size, dtype=torch.int32, device=dev)
-        self.qo_indptr = torch.arange(max_batch_size + 1, dtype=torch.int32, device=dev)
-        self._t = _PagedState(self, "", self.max_num_pages_per_request)
-        self._t.reset()
+        self._alloc_state(max_batch_size, self.max_num_pages_per_request)
         if self.is_spec:
             self.draft_budget, self.window_size = draft_budget, window_size
             self.draft_pages_per_request = draft_budget // PAGE_SIZE + 1
             self.draft_num_pages = self.draft_pages_per_request * max_batch_size
-            self.draft_cachelens = torch.zeros(max_batch_size, dtype=torch.int32, device=dev)
-            self._d = _PagedState(self, "draft_", self.draft_pages_per_request)
-            self._d.reset(last_page_len_init=1, full_table=True)
+            self.draft_cachelens = torch.zeros(max_batch_size, dtype=torch.int32, device=self.device)
+            self._d = _PagedState(self, "draft_", self.draft_pages_per_request, last_page_len_init=1, full_table=True)
             self.model.setup_caches(num_pages=self.max_num_pages, page_size=PAGE_SIZE, spec=True,
                                     draft_num_pages=self.draft_num_pages, draft_budget=draft_budget,
                                     window_size=window_size, max_positions=max_seq_length + 256, kv_dtype=kv_dtype,
@@ -195,43 +285,11 @@ class SnapKVTargetBackend(_BackendBase):
                                     decode_rows=self._decode_rows(self.dec_len, two_token_step=False))
 
     @torch.no_grad()
-    def clear_kv(self):
-        for b in self.model.layers:
-            b.attention.kv_cache.kv_cache.zero_()
-            if self.is_spec:
-                b.attention.kv_cache.draft_cache.zero_()
-        self._reset_kv_calibration()
-        self.cachelens.zero_()
-        self.qo_indptr = torch.arange(self.batch_size + 1, dtype=torch.int32, device=self.device)
-        self._t.reset()
-        if self.is_spec:
-            self.draft_cachelens.zero_()
-            self._d.reset(last_page_len_init=1, full_table=True)
-
-    @torch.no_grad()
     def encode(self, input_ids: torch.LongTensor, benchmark=False):
         """Chunked prefill (backend.py:232-268)."""
         self.clear_kv()
         self._prefill_begin()
-        seq_len = input_ids.shape[1]
-        tokens = None
-        num_chunks = (seq_len + CHUNK - 1) // CHUNK
-        is_last = False
-        done = 0
-        for i in range(num_chunks):
-            ids = input_ids[:, i * CHUNK:min((i + 1) * CHUNK, seq_len)]
-            n = ids.shape[1]
-            if n != CHUNK:
-                is_last = True
-            self._t.map_pages(i + 1, n)                       # pre_encode
-            self.model.skip_head = i != num_chunks - 1
-            self.model.sample_role = "prefill"
-            tokens = self.model.prefill(ids, self.cachelens, self._qo(n), self._t.table(), is_last=is_last,
-                                        draft_tab=self._d.table() if (self.is_spec and is_last) else None,
-                                        ctx_len=done + n)
-            self.cachelens += n
-            done += n
-        self.model.skip_head = False
+        tokens, is_last = self._paged_prefill(input_ids, self._d)
         if self.is_spec:
             if not is_last:
                 raise ValueError("SnapKV self-speculation: prefix_len is a multiple of 128, so no last chunk ran the "
@@ -243,47 +301,23 @@ class SnapKVTargetBackend(_BackendBase):
     @torch.no_grad()
     def inference(self, input_ids: torch.LongTensor, benchmark=False):
         """Autoregressive step / longspec verification (backend.py:129-159)."""
-        n = input_ids.shape[1]
-        self.paged_kv_last_page_len += n                      # pre_decode
-        self.model.sample_role = "verify" if n > 1 else "baseline"
-        out = self._run_step(("fwd", n), lambda ids: self.model.forward(ids, self.cachelens, self._qo(n),
-                                                                          self._t.table()), input_ids)
-        self.cachelens += n
-        if benchmark:
-            self.cachelens -= n
-            self.paged_kv_last_page_len -= n
-        return out
+        role = "verify" if input_ids.shape[1] > 1 else "baseline"
+        return self._step("fwd", self.model.forward, "cachelens", self._t, (self._t,), role, input_ids,
+                          benchmark=benchmark)
 
     @torch.no_grad()
     def verify(self, input_ids: torch.LongTensor, benchmark=False):
         """Self-spec verification: also appends the gamma+1 rows to the draft cache (backend.py:163-197)."""
-        n = input_ids.shape[1]
-        self.paged_kv_last_page_len += n                      # pre_verify
-        self.draft_paged_kv_last_page_len += 1
+        self.draft_paged_kv_last_page_len += 1                # pre_verify; benchmark=True leaves these two as they are
         self.draft_cachelens += 1
-        self.model.sample_role = "verify"
-        out = self._run_step(("verify", n), lambda ids: self.model.verify(ids, self.cachelens, self._qo(n),
-                                                                            self._t.table(), self._d.table()),
-                             input_ids)
-        self.cachelens += n
-        if benchmark:
-            self.cachelens -= n
-            self.paged_kv_last_page_len -= n
-        return out
+        return self._step("verify", self.model.verify, "cachelens", self._t, (self._t, self._d), "verify", input_ids,
+                          benchmark=benchmark)
 
     @torch.no_grad()
     def speculate(self, input_ids: torch.LongTensor, benchmark=False):
         """Self-spec draft step over the SnapKV draft cache (backend.py:200-229)."""
-        n = input_ids.shape[1]
-        self.draft_paged_kv_last_page_len += n                # pre_spec
-        self.model.sample_role = "draft"
-        out = self._run_step(("spec", n), lambda ids: self.model.draft_forward(ids, self.draft_cachelens, self._qo(n),
-                                                                                 self._d.table()), input_ids)
-        self.draft_cachelens += n
-        if benchmark:
-            self.draft_cachelens -= n
-            self.draft_paged_kv_last_page_len -= n
-        return out
+        return self._step("spec", self.model.draft_forward, "draft_cachelens", self._d, (self._d,), "draft", input_ids,
+                          benchmark=benchmark)
 
 
 # ======================================================================================= SnapKV stand-alone draft
@@ -298,20 +332,13 @@ class SnapKVDraftBackend(_BackendBase):
 
     @torch.no_grad()
     def setup_caches(self, max_batch_size: int = 1, max_seq_length: int = 2048, draft_budget=0, window_size=32):
-        self.batch_size = max_batch_size
-        dev = self.device
-        self.page_size = PAGE_SIZE
         self.max_num_pages, self.max_num_pages_per_request = _pages_per_request(max_batch_size, max_seq_length)
-        self.cachelens = torch.zeros(max_batch_size, dtype=torch.int32, device=dev)
-        self.qo_indptr = torch.arange(max_batch_size + 1, dtype=torch.int32, device=dev)
-        self._t = _PagedState(self, "", self.max_num_pages_per_request)
-        self._t.reset()
+        self._alloc_state(max_batch_size, self.max_num_pages_per_request)
         if self.is_compress:
             self.draft_budget, self.window_size = draft_budget, window_size
             self.draft_pages_per_request = draft_budget // PAGE_SIZE + 1
             self.draft_num_pages = self.draft_pages_per_request * max_batch_size
-            self._d = _PagedState(self, "draft_", self.draft_pages_per_request)
-            self._d.reset(last_page_len_init=1, full_table=True)
+            self._d = _PagedState(self, "draft_", self.draft_pages_per_request, last_page_len_init=1, full_table=True)
             self.model.setup_caches(num_pages=self.max_num_pages, page_size=PAGE_SIZE, spec=True,
                                     draft_num_pages=self.draft_num_pages, draft_budget=draft_budget,
                                     window_size=window_size, max_positions=max_seq_length + 256,
@@ -321,42 +348,11 @@ class SnapKVDraftBackend(_BackendBase):
                                     max_positions=max_seq_length + 256, decode_rows=self._decode_rows())
 
     @torch.no_grad()
-    def clear_kv(self):
-        for b in self.model.layers:
-            b.attention.kv_cache.kv_cache.zero_()
-            if self.is_compress:
-                b.attention.kv_cache.draft_cache.zero_()
-        self._reset_kv_calibration()
-        self.cachelens.zero_()
-        self.qo_indptr = torch.arange(self.batch_size + 1, dtype=torch.int32, device=self.device)
-        self._t.reset()
-        if self.is_compress:
-            self._d.reset(last_page_len_init=1, full_table=True)
-
-    @torch.no_grad()
     def encode(self, input_ids: torch.LongTensor, benchmark=False):
         """backend_draft.py:176-209."""
         self.clear_kv()
         self._prefill_begin()
-        seq_len = input_ids.shape[1]
-        tokens = None
-        num_chunks = (seq_len + CHUNK - 1) // CHUNK
-        is_last = False
-        done = 0
-        for i in range(num_chunks):
-            ids = input_ids[:, i * CHUNK:min((i + 1) * CHUNK, seq_len)]
-            n = ids.shape[1]
-            if n != CHUNK:
-                is_last = True
-            self._t.map_pages(i + 1, n)
-            self.model.skip_head = i != num_chunks - 1
-            self.model.sample_role = "prefill"
-            tokens = self.model.prefill(ids, self.cachelens, self._qo(n), self._t.table(), is_last=is_last,
-                                        draft_tab=self._d.table() if (self.is_compress and is_last) else None,
-                                        ctx_len=done + n)
-            self.cachelens += n
-            done += n
-        self.model.skip_head = False
+        tokens, is_last = self._paged_prefill(input_ids, self._d)
         if self.is_compress and not is_last:
             raise ValueError("SnapKV draft: prefix_len is a multiple of 128, so no last chunk ran the select and the "
                              "draft cache is empty (need (prefix_len - window_size) % 128 == 0)")
@@ -366,26 +362,14 @@ class SnapKVDraftBackend(_BackendBase):
     @torch.no_grad()
     def inference(self, input_ids: torch.LongTensor, benchmark=False, cachelen_update=None):
         """One (or, after an all-accept iteration, a two-token) draft step (backend_draft.py:113-173)."""
-        n = input_ids.shape[1]
-        self.model.sample_role = "draft"
-        if self.is_compress:
-            self.draft_paged_kv_last_page_len += n            # pre_decode
-            out = self._run_step(("draft", n), lambda ids: self.model.draft_forward(ids, self.cachelens, self._qo(n),
-                                                                                      self._d.table()), input_ids)
+        if self.is_compress:                                  # pre_decode: into the cache the step reads
+            out = self._step("draft", self.model.draft_forward, "cachelens", self._d, (self._d,), "draft", input_ids,
+                             cachelen_update)
         else:
-            self.paged_kv_last_page_len += n
-            out = self._run_step(("fwd", n), lambda ids: self.model.forward(ids, self.cachelens, self._qo(n),
-                                                                              self._t.table()), input_ids)
-        if cachelen_update is None:
-            self.cachelens += n
-        else:
-            cu = cachelen_update.to(torch.int32).flatten()
-            self.cachelens += cu
-            if self.is_compress:
-                self.draft_paged_kv_last_page_len = self.draft_paged_kv_last_page_len - n + cu
-            else:
-                self.paged_kv_last_page_len = self.paged_kv_last_page_len - n + cu
+            out = self._step("fwd", self.model.forward, "cachelens", self._t, (self._t,), "draft", input_ids,
+                             cachelen_update)
         if benchmark:   # as the reference: always the un-prefixed table (backend_draft.py:139-142)
+            n = input_ids.shape[1]
             self.cachelens -= n
             self.paged_kv_last_page_len -= n
         return out
@@ -397,21 +381,14 @@ class _StreamingMixin:
 
     def _stream_encode(self, input_ids, state: _PagedState, lens_attr, which):
         self._prefill_begin()
-        seq_len = input_ids.shape[1]
         tokens = None
-        num_chunks = (seq_len + CHUNK - 1) // CHUNK
-        is_last = False
         ctx = 0                                       # host mirror of the (capped) cache length
-        for i in range(num_chunks):
-            ids = input_ids[:, i * CHUNK:min((i + 1) * CHUNK, seq_len)]
-            n = ids.shape[1]
-            if n != CHUNK:
-                is_last = True
+        for ids, n, is_last, final in _chunks(input_ids):
             if ctx + n <= self.draft_budget:          # pre_encode (StreamingLLM/backend_draft.py:155-192)
                 state.map_pages(state.host_pages + 1, n)
             else:
                 state.map_pages(state.ppr, self.draft_budget % PAGE_SIZE)
-            self.model.skip_head = i != num_chunks - 1
+            self.model.skip_head = not final
             self.model.sample_role = "prefill"
             tokens = self.model.stream_prefill(ids, ctx, self._qo(n), state.table(), is_last, which, self.batch_size)
             ctx += n
@@ -434,27 +411,13 @@ class StreamingDraftBackend(_BackendBase, _StreamingMixin):
 
     @torch.no_grad()
     def setup_caches(self, max_batch_size: int = 1, draft_budget=0):
-        self.draft_budget, self.batch_size = draft_budget, max_batch_size
-        dev = self.device
-        self.page_size = PAGE_SIZE
+        self.draft_budget = draft_budget
         self.max_num_pages_per_request = draft_budget // PAGE_SIZE + 1
         self.max_num_pages = self.max_num_pages_per_request * max_batch_size
-        self.cachelens = torch.zeros(max_batch_size, dtype=torch.int32, device=dev)
-        self.qo_indptr = torch.arange(max_batch_size + 1, dtype=torch.int32, device=dev)
-        self._t = _PagedState(self, "", self.max_num_pages_per_request)
-        self._t.reset()
+        self._alloc_state(max_batch_size, self.max_num_pages_per_request)
         self.model.setup_caches(num_pages=self.max_num_pages, page_size=PAGE_SIZE, draft_budget=draft_budget,
                                 streaming=True, max_positions=self.max_num_pages_per_request * PAGE_SIZE + 256,
                                 decode_rows=self._decode_rows())
-
-    @torch.no_grad()
-    def clear_kv(self):
-        for b in self.model.layers:
-            b.attention.kv_cache.kv_cache.zero_()
-        self._reset_kv_calibration()
-        self.cachelens.zero_()
-        self.qo_indptr = torch.arange(self.batch_size + 1, dtype=torch.int32, device=self.device)
-        self._t.reset()
 
     @torch.no_grad()
     def encode(self, input_ids: torch.LongTensor, benchmark=False):
@@ -464,21 +427,8 @@ class StreamingDraftBackend(_BackendBase, _StreamingMixin):
     @torch.no_grad()
     def inference(self, input_ids: torch.LongTensor, benchmark=False, cachelen_update=None):
         """StreamingLLM/backend_draft.py:89-124."""
-        n = input_ids.shape[1]
-        self.model.sample_role = "draft"
-        self.paged_kv_last_page_len += n
-        out = self._run_step(("fwd", n), lambda ids: self.model.forward(ids, self.cachelens, self._qo(n),
-                                                                          self._t.table()), input_ids)
-        if cachelen_update is None:
-            self.cachelens += n
-        else:
-            cu = cachelen_update.to(torch.int32).flatten()
-            self.cachelens += cu
-            self.paged_kv_last_page_len = self.paged_kv_last_page_len - n + cu
-        if benchmark:
-            self.cachelens -= n
-            self.paged_kv_last_page_len -= n
-        return out
+        return self._step("fwd", self.model.forward, "cachelens", self._t, (self._t,), "draft", input_ids,
+                          cachelen_update, benchmark)
 
 
 class StreamingSelfSpecBackend(_BackendBase, _StreamingMixin):
@@ -494,53 +444,25 @@ class StreamingSelfSpecBackend(_BackendBase, _StreamingMixin):
     def setup_caches(self, max_batch_size: int = 1, max_seq_length: int = 2048, draft_budget=0, kv_dtype="bf16",
                      kv_layout=None):
         kv_layout = default_kv_layout() if kv_layout is None else kv_layout
-        self.draft_budget, self.batch_size = draft_budget, max_batch_size
-        dev = self.device
-        self.page_size = PAGE_SIZE
+        self.draft_budget = draft_budget
         self.max_num_pages, self.max_num_pages_per_request = _pages_per_request(max_batch_size, max_seq_length)
-        self.cachelens = torch.zeros(max_batch_size, dtype=torch.int32, device=dev)
-        self.draft_cachelens = torch.zeros(max_batch_size, dtype=torch.int32, device=dev)
-        self.qo_indptr = torch.arange(max_batch_size + 1, dtype=torch.int32, device=dev)
+        self._alloc_state(max_batch_size, self.max_num_pages_per_request)
+        self.draft_cachelens = torch.zeros(max_batch_size, dtype=torch.int32, device=self.device)
         self.draft_max_num_pages_per_request = draft_budget // PAGE_SIZE + 1
         self.draft_max_num_pages = self.draft_max_num_pages_per_request * max_batch_size
-        self._t = _PagedState(self, "", self.max_num_pages_per_request)
-        self._d = _PagedState(self, "draft_", self.draft_max_num_pages_per_request)
-        self._t.reset()
-        self._d.reset(indptr_stride=self.draft_max_num_pages_per_request)
+        self._d = _PagedState(self, "draft_", self.draft_max_num_pages_per_request,
+                              indptr_stride=self.draft_max_num_pages_per_request)   # StreamingLLM/backend.py:316
         self.model.setup_caches(num_pages=self.max_num_pages, page_size=PAGE_SIZE, spec=True,
                                 draft_num_pages=self.draft_max_num_pages, draft_budget=draft_budget, streaming=True,
                                 max_positions=max_seq_length + 256, kv_dtype=kv_dtype, kv_layout=kv_layout,
                                 decode_rows=self._decode_rows(self.dec_len))
 
     @torch.no_grad()
-    def clear_kv(self):
-        for b in self.model.layers:
-            b.attention.kv_cache.kv_cache.zero_()
-            b.attention.kv_cache.draft_cache.zero_()
-        self._reset_kv_calibration()
-        self.cachelens.zero_()
-        self.draft_cachelens.zero_()
-        self.qo_indptr = torch.arange(self.batch_size + 1, dtype=torch.int32, device=self.device)
-        self._t.reset()
-        self._d.reset(indptr_stride=self.draft_max_num_pages_per_request)   # StreamingLLM/backend.py:316
-
-    @torch.no_grad()
     def encode(self, input_ids: torch.LongTensor, benchmark=False):
         """Target prefill (StreamingLLM/backend.py:190-211)."""
         self.clear_kv()
         self._prefill_begin()
-        seq_len = input_ids.shape[1]
-        tokens = None
-        num_chunks = (seq_len + CHUNK - 1) // CHUNK
-        for i in range(num_chunks):
-            ids = input_ids[:, i * CHUNK:min((i + 1) * CHUNK, seq_len)]
-            n = ids.shape[1]
-            self._t.map_pages(i + 1, n)
-            self.model.skip_head = i != num_chunks - 1
-            self.model.sample_role = "prefill"
-            tokens = self.model.prefill(ids, self.cachelens, self._qo(n), self._t.table())
-            self.cachelens += n
-        self.model.skip_head = False
+        tokens, _ = self._paged_prefill(input_ids)
         self._prefill_end()
         return tokens
 
@@ -551,32 +473,10 @@ class StreamingSelfSpecBackend(_BackendBase, _StreamingMixin):
 
     @torch.no_grad()
     def verify(self, input_ids: torch.LongTensor, benchmark=False):
-        n = input_ids.shape[1]
-        self.paged_kv_last_page_len += n
-        self.model.sample_role = "verify"
-        out = self._run_step(("verify", n), lambda ids: self.model.verify(ids, self.cachelens, self._qo(n),
-                                                                            self._t.table()), input_ids)
-        self.cachelens += n
-        if benchmark:
-            self.cachelens -= n
-            self.paged_kv_last_page_len -= n
-        return out
+        return self._step("verify", self.model.verify, "cachelens", self._t, (self._t,), "verify", input_ids,
+                          benchmark=benchmark)
 
     @torch.no_grad()
     def speculate(self, input_ids: torch.LongTensor, benchmark=False, cachelen_update=None):
-        n = input_ids.shape[1]
-        self.draft_paged_kv_last_page_len += n
-        self.model.sample_role = "draft"
-        out = self._run_step(("spec", n), lambda ids: self.model.draft_forward(ids, self.draft_cachelens,
-                                                                                 self._qo(n), self._d.table()),
-                             input_ids)
-        if cachelen_update is None:
-            self.draft_cachelens += n
-        else:
-            cu = cachelen_update.to(torch.int32).flatten()
-            self.draft_cachelens += cu
-            self.draft_paged_kv_last_page_len = self.draft_paged_kv_last_page_len - n + cu
-        if benchmark:
-            self.draft_cachelens -= n
-            self.draft_paged_kv_last_page_len -= n
-        return out
+        return self._step("spec", self.model.draft_forward, "draft_cachelens", self._d, (self._d,), "draft", input_ids,
+                          cachelen_update, benchmark)

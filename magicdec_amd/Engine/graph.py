@@ -7,7 +7,8 @@ memory at execution time and nothing in a step touches the host, so a step is ca
 (kind, n_tokens) and replayed.
 
 The harness may REBIND the length tensors between calls (tests/SnapKV/longspec_benchmark.py:228-256).  Graphs
-bake addresses, so each captured step owns static copies of the state tensors it reads; before a replay any
+bake addresses, so each captured step owns static copies of the state tensors it reads -- the caller names them
+(_BackendBase._step: the length tensor, qo_indptr and the tensors of the page tables it passes); before a replay any
 attribute that is no longer the static tensor is copied into it and re-bound to it (same values, so the
 reference's semantics are unchanged); in the steady state of our own loop (in-place updates) nothing is copied.
 """
@@ -16,16 +17,6 @@ from __future__ import annotations
 import warnings
 
 import torch
-
-_STATE_BY_KIND = {
-    "fwd": ("cachelens", "qo_indptr", "paged_kv_indices", "paged_kv_indptr", "paged_kv_last_page_len"),
-    "draft": ("cachelens", "qo_indptr", "draft_paged_kv_indices", "draft_paged_kv_indptr",
-              "draft_paged_kv_last_page_len"),
-    "spec": ("draft_cachelens", "qo_indptr", "draft_paged_kv_indices", "draft_paged_kv_indptr",
-             "draft_paged_kv_last_page_len"),
-    "verify": ("cachelens", "qo_indptr", "paged_kv_indices", "paged_kv_indptr", "paged_kv_last_page_len",
-               "draft_paged_kv_indices", "draft_paged_kv_indptr", "draft_paged_kv_last_page_len"),
-}
 
 
 class _Captured:
@@ -115,8 +106,9 @@ def _recover_from_failed_capture(g, home_stream):
             pass
 
 
-def run_captured(backend, key, fn, input_ids):
-    kind = key[0]
+def run_captured(backend, key, names, fn, input_ids):
+    """Run step `key` = (kind, n_tokens) of `backend` as a graph replay.  `names`: the state attributes `fn` reads -- the
+    length tensor, qo_indptr and the three tensors of every page table it passes on (_BackendBase._step knows them)."""
     full_key = (key, tuple(input_ids.shape), tuple(getattr(backend, "paged_kv_indices").shape),
                 tuple(getattr(backend, "draft_paged_kv_indices").shape) if hasattr(backend, "draft_paged_kv_indices")
                 else None)
@@ -124,14 +116,10 @@ def run_captured(backend, key, fn, input_ids):
     if ent is None:
         ent = _Captured()
         gs = _statics(backend)
-        names = []
-        for name in _STATE_BY_KIND[kind]:
-            cur = getattr(backend, name, None)
-            if cur is None:
-                continue
+        for name in names:
+            cur = getattr(backend, name)
             if name not in gs or gs[name].shape != cur.shape:
                 gs[name] = cur.clone()
-            names.append(name)
         ent.names = tuple(names)
         _bind_state(backend, ent)
         ent.static_in = input_ids.clone()

@@ -347,27 +347,61 @@ def test_hip_loop_equals_hip_autoregressive(ckpt_dir):
     assert st.iters > 0 and total > 0
 
 
-def test_hipgraph_steps_equal_eager_steps(ckpt_dir):
+# case -> (the _hip kinds of its engines, the reference trace of the same loop on the same tiny models, if the loop has
+# a two-token step)
+HIPGRAPH_CASES = {
+    "longspec/snapkv_draft": (("target", "snapkv_draft"), "run_longspec_snapkv.json"),
+    "longspec/stream_draft": (("target", "stream_draft"), "run_longspec_stream.json"),
+    "snapkv_self": (("snapkv_self",), None),
+    "stream_self": (("stream_self",), "run_selfspec_stream.json"),
+}
+HIPGRAPH_BATCH = 1      # of gc.synthetic_batches(): the reference's own traces show two-token steps in it (checked below)
+
+
+def _reference_two_token_steps(golden, batch):
+    """cachelen_update records of batch `batch` in a committed reference trace (a batch starts with the first call's kind)."""
+    trace = gc.load_json(golden)["trace"]
+    first, b, n = (trace[0]["cls"], trace[0]["fn"]), -1, 0
+    for r in trace:
+        b += (r["cls"], r["fn"]) == first
+        n += b == batch and "cachelen_update" in r
+    return n
+
+
+@pytest.mark.parametrize("case", list(HIPGRAPH_CASES))
+def test_hipgraph_steps_equal_eager_steps(case, ckpt_dir):
     """engine.compile() (hipGraph capture of the decode steps, Engine/graph.py) must not change a single token or
-    length: the free-running longspec loop with graphs == without graphs, bit for bit (same kernels, deterministic)."""
+    length: each free-running loop with graphs == without graphs, bit for bit (same kernels, deterministic) -- output,
+    num_nodes, the accept trace and every length / last-page tensor of every engine.  Every loop that has one must run
+    its two-token step (after an all-accept iteration) under graphs: that step REBINDS the last-page length it advanced
+    (`cachelen_update`), which a captured step that does not pin every tensor it reads would miss."""
     from magicdec_amd import harness
-    ids = gc.synthetic_batches()[1].to(DEV)
+    kinds, golden = HIPGRAPH_CASES[case]
+    assert golden is None or _reference_two_token_steps(golden, HIPGRAPH_BATCH) > 0
+    ids = gc.synthetic_batches()[HIPGRAPH_BATCH].to(DEV)
     outs = []
     for use_graphs in (False, True):
-        tgt, drf = _hip("target", ckpt_dir), _hip("snapkv_draft", ckpt_dir)
+        engines = [_hip(k, ckpt_dir) for k in kinds]
         if use_graphs:
-            tgt.compile()
-            drf.compile()
+            for e in engines:
+                e.compile()
         trace = []
-        st, _ = harness.run_longspec_batch(tgt, drf, ids, gc.GAMMA, gc.MAX_LEN, gc.EOT_1, gc.EOT_2,
-                                           trace_fn=lambda s: trace.append(s.accept_nums.tolist()))
-        outs.append((st.output.cpu(), st.num_nodes.cpu(), trace, tgt.cachelens.cpu(), drf.cachelens.cpu(),
-                     drf.draft_paged_kv_last_page_len.cpu()))
-    a, b = outs
-    assert a[2] == b[2] and len(a[2]) > 3, "accept traces differ"
+        kw = dict(trace_fn=lambda s: trace.append(s.accept_nums.tolist()))
+        if len(engines) == 2:
+            st, _ = harness.run_longspec_batch(*engines, ids, gc.GAMMA, gc.MAX_LEN, gc.EOT_1, gc.EOT_2, **kw)
+        else:
+            st, _ = harness.run_selfspec_batch(engines[0], ids, gc.GAMMA, gc.MAX_LEN, gc.EOT_1, gc.EOT_2,
+                                               case == "stream_self", **kw)
+        assert not use_graphs or all(e._use_graphs and e._graphs for e in engines), "a capture fell back to eager"
+        state = [getattr(e, k).cpu() for e in engines for k in MUT if getattr(e, k, None) is not None]
+        outs.append((trace, [st.output.cpu(), st.num_nodes.cpu()] + state))
+    (trace_a, a), (trace_b, b) = outs
+    assert trace_a == trace_b and len(trace_a) > 3, "accept traces differ"
+    assert len(a) == len(b) >= 2 + 2 * len(kinds)
     for x, y in zip(a, b):
-        if torch.is_tensor(x):
-            assert torch.equal(x, y)
+        assert torch.equal(x, y)
+    if golden is not None:      # an all-accept iteration that was not the last: the next one began with the two-token step
+        assert any(max(acc) == gc.GAMMA + 1 for acc in trace_b[:-1]), trace_b
 
 
 # ------------------------------------------------------------------ other model families of the reference's zoo

@@ -755,6 +755,32 @@ def test_fp8_kv_cache_host_logic(cpu_ops_patched, ckpt_dir):
         d.model.setup_caches(num_pages=4, streaming=True, draft_budget=gc.BUDGET, kv_dtype="fp8")
 
 
+def test_fp8_kv_scales_are_recalibrated_by_every_encode(cpu_ops_patched, ckpt_dir):
+    """The static fp8 scales belong to ONE prompt: every encode() (through clear_kv) re-arms the calibration, so a second
+    prompt is quantised with the scales of its own first chunk -- those a fresh engine finds for it -- not the first's."""
+    from magicdec_amd.Engine.SnapKV.backend import LMBackend
+
+    def engine():
+        eng = LMBackend(dtype=torch.bfloat16, device="cpu", dec_len=gc.GAMMA + 1)
+        eng.load_model(ckpt_dir / "tinytgt" / "model.pth", use_tp=False)
+        eng.setup_caches(max_batch_size=gc.B, max_seq_length=gc.MAX_LEN, kv_dtype="fp8")
+        return eng
+
+    def scales(eng):
+        return [s.clone() for b in eng.model.layers for s in (b.attention.kv_cache.k_scale, b.attention.kv_cache.v_scale)]
+    first, second = gc.synthetic_batches()[:2]
+    eng, fresh = engine(), engine()
+    eng.encode(first)
+    of_first = scales(eng)
+    eng.clear_kv()
+    assert not any(b.attention.kv_cache.calibrated for b in eng.model.layers)
+    eng.encode(second)
+    fresh.encode(second)
+    assert all(b.attention.kv_cache.calibrated for b in eng.model.layers)
+    assert all(torch.equal(x, y) for x, y in zip(scales(eng), scales(fresh)))
+    assert any(not torch.equal(x, y) for x, y in zip(scales(eng), of_first))
+
+
 def test_hnd_page_layout_host_logic(cpu_ops_patched, ckpt_dir):
     """kv_layout="HND" (flashinfer's other page layout; the reference plans "NHD"): the full-context cache is allocated
     [pages, 2, KH, 128, D], the compressed draft cache stays NHD, every op on the full cache is told the layout, and the
@@ -1676,3 +1702,22 @@ def test_one_resident_copy_per_weight_release_and_restore():
     # without announced row counts nothing is released (any row count may come)
     m2 = build("dedupe_any", None, n_head=32, n_local_heads=8, dim=2048, intermediate_size=8192)
     assert m2.release_rowmajor() == 0 and m2.packed_bytes > 0
+
+
+def test_backend_step_trace_equals_the_committed_parent_trace(monkeypatch):
+    """tools/backend_step_trace.py on this tree against the trace recorded on the commit BEFORE the back-ends' step, prefill
+    and clear bodies were shared (profiles/backend_step_trace_parent.txt): every call the back-ends make into their model
+    -- method, n, sample_role / skip_head, which attribute each page-table tensor and the length tensor is, their values --
+    and every attribute a back-end call rebinds, over the first iterations of the five loops and the benchmark=True
+    programs, byte for byte."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("backend_step_trace", ROOT / "tools" / "backend_step_trace.py")
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    got = tool.trace(monkeypatch).splitlines()
+    want = (ROOT / "profiles" / "backend_step_trace_parent.txt").read_text().splitlines()
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert a == b, (i + 1, a, b)
+    assert len(got) == len(want)
+    assert sum("cachelen_update=[" in line for line in got) >= 5 and sum("benchmark=True" in line for line in got) >= 8
+    assert (ROOT / "profiles" / "backend_step_trace_branch.txt").read_text().splitlines() == want
