@@ -141,6 +141,79 @@ def _dataset(args, tokenizer, vocab):
                                 num_sequences=10 * args.B)
 
 
+def _setup(args, longspec=False):
+    """What every entry point does first: the device, the process groups under tensor parallelism, prints on the first
+    target rank only, the seed.  longspec: those two scripts key tensor parallelism on the size of
+    --draft_rank_group and get a draft sub-group as well (tests/SnapKV/longspec_benchmark.py:60-66); the others key it
+    on --rank_group.  Returns (device, use_tp, rank, global_group, draft_group, print_)."""
+    DEVICE = _device()
+    use_tp = len(args.draft_rank_group if longspec else args.rank_group) > 1
+    rank, global_group, draft_group = 0, None, None
+    print_ = builtins.print
+    if use_tp:
+        from .Engine.tp import init_dist
+        if longspec:
+            rank, global_group, draft_group = init_dist(args.draft_rank_group)
+        else:
+            rank, global_group = init_dist()
+        if rank != args.rank_group[0]:
+            print_ = lambda *a, **k: None
+        DEVICE = f"cuda:{rank}" if torch.cuda.is_available() else "cpu"
+    setup_seed(args.seed)
+    print_(f"Using device={DEVICE}")
+    return DEVICE, use_tp, rank, global_group, draft_group, print_
+
+
+def _data(args, engine, print_):
+    """Tokenizer, EOT ids and the evaluation batches.  Returns (tokenizer, eot_1, eot_2, dataloader, num_eval_steps)."""
+    tokenizer = load_tokenizer(args.model_name)
+    eot_1, eot_2 = _eot(tokenizer)
+    print_(f"eot_1: {eot_1}, eot_2: {eot_2}")
+    dataset = _dataset(args, tokenizer, engine.model.tok_embeddings.weight.shape[0])
+    dataloader = DataLoader(dataset, batch_size=args.B, shuffle=False, drop_last=True)
+    return tokenizer, eot_1, eot_2, dataloader, min(10, len(dataloader))
+
+
+def _evaluate(args, run_batch, tokenizer, dataloader, num_eval_steps, DEVICE, use_tp, print_, avg_latency=False):
+    """The evaluation loop of the four speculative scripts (tests/SnapKV/longspec_benchmark.py:131-319 and its three
+    twins): run_batch(input_ids, timers) -> (state, seconds) per batch, the report lines, the totals reset after each
+    of the first five batches.  avg_latency: only tests/SnapKV/longspec_benchmark.py:305 prints the latency; its
+    StreamingLLM twin (:302) and the self-speculation scripts do not."""
+    BATCH_SIZE = args.B
+    total_time, num_gen_tokens, target_steps = 0.0, 0, 0
+    timers = harness.PhaseTimers(DEVICE) if args.benchmark else None
+    for step, batch in enumerate(dataloader):
+        if step >= num_eval_steps:
+            break
+        input_ids = batch[0].to(DEVICE)
+        st, dt = run_batch(input_ids, timers)
+        total_time += dt
+        target_steps += st.iters
+        num_gen_tokens += int(st.num_nodes.sum() - (input_ids.shape[1] + 1) * BATCH_SIZE)
+        if args.printoutput:
+            for i in range(BATCH_SIZE):
+                print_("Sequence ", i)
+                print_(tokenizer.decode(st.output[i, args.prefix_len:st.num_nodes[i]]))
+        if avg_latency:
+            print_("total time :{:.5f}s, time per iter :{:.5f}s, decoding step: {}, large model step: {}, avg latency: {}".format(
+                total_time, total_time / target_steps, num_gen_tokens, target_steps, total_time / num_gen_tokens * BATCH_SIZE))
+        else:
+            print_("total time :{:.5f}s, time per iter :{:.5f}s, decoding step: {}, large model step: {}".format(
+                total_time, total_time / target_steps, num_gen_tokens, target_steps))
+        if args.benchmark:     # tests/SnapKV/longspec_benchmark.py:305-307, the same line in the other three scripts
+            print_("target time :{:.5f}s, draft time :{:.5f}s, verify loop : {}, avg generate len per sentence: {}".format(
+                timers.target / target_steps, timers.draft / target_steps, timers.verify_loop / target_steps,
+                _avg_len(num_gen_tokens, target_steps, BATCH_SIZE)))
+        if step < 5:
+            total_time, num_gen_tokens, target_steps = 0.0, 0, 0
+            if timers is not None:
+                timers.reset()
+        if use_tp:
+            dist.barrier()
+    print_(f"Final tokens per second :{num_gen_tokens / total_time}")
+    return num_gen_tokens / total_time
+
+
 def longspec_main(kind: str, argv=None):
     """kind: 'SnapKV' | 'StreamingLLM' -- tests/<kind>/longspec_benchmark.py."""
     args = parse_entry_args(longspec_parser(kind), argv)
@@ -153,20 +226,7 @@ def longspec_main(kind: str, argv=None):
     else:
         assert (args.draft_budget - 1) % 128 == 0
 
-    draft_tp = len(args.draft_rank_group) > 1
-    DEVICE = _device()
-    from .Engine.tp import init_dist
-    use_tp = len(args.draft_rank_group) > 1
-    global_group = draft_group = None
-    rank = 0
-    print_ = builtins.print
-    if use_tp:
-        rank, global_group, draft_group = init_dist(args.draft_rank_group)
-        if rank != args.rank_group[0]:
-            print_ = lambda *a, **k: None
-        DEVICE = f"cuda:{rank}" if torch.cuda.is_available() else "cpu"
-    setup_seed(args.seed)
-    print_(f"Using device={DEVICE}")
+    DEVICE, use_tp, rank, global_group, draft_group, print_ = _setup(args, longspec=True)
     replicate = bool(getattr(args, "replicate_draft", False)) and use_tp
     draft_target_equal = len(args.draft_rank_group) == len(args.rank_group) or replicate
     MAX_LEN_TARGET, BATCH_SIZE, DTYPE = args.max_len, args.B, torch.bfloat16
@@ -189,7 +249,7 @@ def longspec_main(kind: str, argv=None):
             draft = LMBackend_Draft(dtype=DTYPE, device=DEVICE, draft_budget=args.draft_budget)
         else:
             draft = LMBackend_Draft(dtype=DTYPE, device=DEVICE)
-        draft.load_model(args.model, use_tp=use_tp and draft_tp and not replicate, rank_group=args.draft_rank_group,
+        draft.load_model(args.model, use_tp=use_tp and not replicate, rank_group=args.draft_rank_group,
                          group=draft_group)
         if replicate:       # every rank runs the whole draft and must choose the same kernels (Transformer._pack_weights)
             draft.model.replica_group = global_group
@@ -202,49 +262,15 @@ def longspec_main(kind: str, argv=None):
     if use_tp:
         dist.barrier()
 
-    tokenizer = load_tokenizer(args.model_name)
-    eot_1, eot_2 = _eot(tokenizer)
-    print_(f"eot_1: {eot_1}, eot_2: {eot_2}")
-    dataset = _dataset(args, tokenizer, engine.model.tok_embeddings.weight.shape[0])
-    dataloader = DataLoader(dataset, batch_size=BATCH_SIZE, shuffle=False, drop_last=True)
-    num_eval_steps = min(10, len(dataloader))
+    tokenizer, eot_1, eot_2, dataloader, num_eval_steps = _data(args, engine, print_)
     bcast = (args.draft_rank_group[0], global_group) if (use_tp and not draft_target_equal) else None
     sampler = _sampler(args, engine, args.gamma, DEVICE)
     barrier = dist.barrier if use_tp else None
-
-    total_time, num_gen_tokens, target_steps = 0.0, 0, 0
-    timers = harness.PhaseTimers(DEVICE) if args.benchmark else None
-    for step, batch in enumerate(dataloader):
-        if step >= num_eval_steps:
-            break
-        input_ids = batch[0].to(DEVICE)
-        st, dt = harness.run_longspec_batch(engine, draft, input_ids, args.gamma, MAX_LEN_TARGET, eot_1, eot_2,
-                                            bcast=bcast, barrier=barrier, timers=timers, sampler=sampler)
-        total_time += dt
-        target_steps += st.iters
-        num_gen_tokens += int(st.num_nodes.sum() - (input_ids.shape[1] + 1) * BATCH_SIZE)
-        if args.printoutput:
-            for i in range(BATCH_SIZE):
-                print_("Sequence ", i)
-                print_(tokenizer.decode(st.output[i, args.prefix_len:st.num_nodes[i]]))
-        if kind == "SnapKV":   # only tests/SnapKV/longspec_benchmark.py:305 prints the latency; the StreamingLLM twin (:302) not
-            print_("total time :{:.5f}s, time per iter :{:.5f}s, decoding step: {}, large model step: {}, avg latency: {}".format(
-                total_time, total_time / target_steps, num_gen_tokens, target_steps, total_time / num_gen_tokens * BATCH_SIZE))
-        else:
-            print_("total time :{:.5f}s, time per iter :{:.5f}s, decoding step: {}, large model step: {}".format(
-                total_time, total_time / target_steps, num_gen_tokens, target_steps))
-        if args.benchmark:     # tests/SnapKV/longspec_benchmark.py:305-307
-            print_("target time :{:.5f}s, draft time :{:.5f}s, verify loop : {}, avg generate len per sentence: {}".format(
-                timers.target / target_steps, timers.draft / target_steps, timers.verify_loop / target_steps,
-                _avg_len(num_gen_tokens, target_steps, BATCH_SIZE)))
-        if step < 5:
-            total_time, num_gen_tokens, target_steps = 0.0, 0, 0
-            if timers is not None:
-                timers.reset()
-        if use_tp:
-            dist.barrier()
-    print_(f"Final tokens per second :{num_gen_tokens / total_time}")
-    return num_gen_tokens / total_time
+    return _evaluate(
+        args, lambda input_ids, timers: harness.run_longspec_batch(
+            engine, draft, input_ids, args.gamma, MAX_LEN_TARGET, eot_1, eot_2, bcast=bcast, barrier=barrier,
+            timers=timers, sampler=sampler),
+        tokenizer, dataloader, num_eval_steps, DEVICE, use_tp, print_, avg_latency=kind == "SnapKV")
 
 
 def selfspec_main(kind: str, argv=None):
@@ -255,19 +281,7 @@ def selfspec_main(kind: str, argv=None):
     assert (args.draft_budget - 1) % 128 == 0
     if kind == "SnapKV":
         assert (args.prefix_len - args.window_size) % 128 == 0
-    DEVICE = _device()
-    use_tp = len(args.rank_group) > 1
-    global_group = None
-    rank = 0
-    print_ = builtins.print
-    if use_tp:
-        from .Engine.tp import init_dist
-        rank, global_group = init_dist()
-        if rank != args.rank_group[0]:
-            print_ = lambda *a, **k: None
-        DEVICE = f"cuda:{rank}" if torch.cuda.is_available() else "cpu"
-    setup_seed(args.seed)
-    print_(f"Using device={DEVICE}")
+    DEVICE, use_tp, _, global_group, _, print_ = _setup(args)
     MAX_LEN_TARGET, BATCH_SIZE, DTYPE = args.max_len, args.B, torch.bfloat16
     streaming = kind == "StreamingLLM"
     if streaming:
@@ -285,42 +299,12 @@ def selfspec_main(kind: str, argv=None):
     else:
         engine.setup_caches(max_batch_size=BATCH_SIZE, max_seq_length=MAX_LEN_TARGET, draft_budget=args.draft_budget,
                             window_size=args.window_size, kv_dtype=args.kv_dtype, kv_layout=args.kv_layout)
-    tokenizer = load_tokenizer(args.model_name)
-    eot_1, eot_2 = _eot(tokenizer)
-    print_(f"eot_1: {eot_1}, eot_2: {eot_2}")
-    dataset = _dataset(args, tokenizer, engine.model.tok_embeddings.weight.shape[0])
-    dataloader = DataLoader(dataset, batch_size=BATCH_SIZE, shuffle=False, drop_last=True)
-    num_eval_steps = min(10, len(dataloader))
+    tokenizer, eot_1, eot_2, dataloader, num_eval_steps = _data(args, engine, print_)
     sampler = _sampler(args, engine, args.gamma, DEVICE)
-    total_time, num_gen_tokens, target_steps = 0.0, 0, 0
-    timers = harness.PhaseTimers(DEVICE) if args.benchmark else None
-    for step, batch in enumerate(dataloader):
-        if step >= num_eval_steps:
-            break
-        input_ids = batch[0].to(DEVICE)
-        st, dt = harness.run_selfspec_batch(engine, input_ids, args.gamma, MAX_LEN_TARGET, eot_1, eot_2, streaming,
-                                            timers=timers, sampler=sampler)
-        total_time += dt
-        target_steps += st.iters
-        num_gen_tokens += int(st.num_nodes.sum() - (input_ids.shape[1] + 1) * BATCH_SIZE)
-        if args.printoutput:
-            for i in range(BATCH_SIZE):
-                print_("Sequence ", i)
-                print_(tokenizer.decode(st.output[i, args.prefix_len:st.num_nodes[i]]))
-        print_("total time :{:.5f}s, time per iter :{:.5f}s, decoding step: {}, large model step: {}".format(
-            total_time, total_time / target_steps, num_gen_tokens, target_steps))
-        if args.benchmark:     # tests/SnapKV/selfspec_benchmark.py (same line as the longspec script)
-            print_("target time :{:.5f}s, draft time :{:.5f}s, verify loop : {}, avg generate len per sentence: {}".format(
-                timers.target / target_steps, timers.draft / target_steps, timers.verify_loop / target_steps,
-                _avg_len(num_gen_tokens, target_steps, BATCH_SIZE)))
-        if step < 5:
-            total_time, num_gen_tokens, target_steps = 0.0, 0, 0
-            if timers is not None:
-                timers.reset()
-        if use_tp:
-            dist.barrier()
-    print_(f"Final tokens per second :{num_gen_tokens / total_time}")
-    return num_gen_tokens / total_time
+    return _evaluate(
+        args, lambda input_ids, timers: harness.run_selfspec_batch(
+            engine, input_ids, args.gamma, MAX_LEN_TARGET, eot_1, eot_2, streaming, timers=timers, sampler=sampler),
+        tokenizer, dataloader, num_eval_steps, DEVICE, use_tp, print_)
 
 
 def baseline_main(argv=None):
@@ -328,19 +312,7 @@ def baseline_main(argv=None):
     args = parse_entry_args(baseline_parser(), argv)
     assert args.prefix_len < args.max_len          # tests/baseline_benchmark.py:30-31
     assert args.max_len % 128 == 0
-    DEVICE = _device()
-    use_tp = len(args.rank_group) > 1
-    global_group = None
-    rank = 0
-    print_ = builtins.print
-    if use_tp:
-        from .Engine.tp import init_dist
-        rank, global_group = init_dist()
-        if rank != args.rank_group[0]:
-            print_ = lambda *a, **k: None
-        DEVICE = f"cuda:{rank}" if torch.cuda.is_available() else "cpu"
-    setup_seed(args.seed)
-    print_(f"Using device={DEVICE}")
+    DEVICE, use_tp, _, global_group, _, print_ = _setup(args)
     from .Engine.SnapKV.backend import LMBackend
     engine = LMBackend(dtype=torch.bfloat16, device=DEVICE)
     engine.load_model(args.model, use_tp=use_tp, rank_group=args.rank_group, group=global_group)
@@ -348,12 +320,7 @@ def baseline_main(argv=None):
         engine.compile()
     engine.setup_caches(max_batch_size=args.B, max_seq_length=args.max_len, kv_dtype=args.kv_dtype,
                         kv_layout=args.kv_layout)
-    tokenizer = load_tokenizer(args.model_name)
-    eot_1, eot_2 = _eot(tokenizer)
-    print_(f"eot_1: {eot_1}, eot_2: {eot_2}")
-    dataset = _dataset(args, tokenizer, engine.model.tok_embeddings.weight.shape[0])
-    dataloader = DataLoader(dataset, batch_size=args.B, shuffle=False, drop_last=True)
-    num_eval_steps = min(10, len(dataloader))
+    tokenizer, eot_1, eot_2, dataloader, num_eval_steps = _data(args, engine, print_)
     sampler = _sampler(args, engine, 0, DEVICE)
     total_time, model_steps = 0.0, 0
     for step, batch in enumerate(dataloader):

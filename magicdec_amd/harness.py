@@ -64,9 +64,9 @@ def new_state(B, gamma, out_cols, device, input_ids=None):
 _SPIN_ON_HOST_READ = os.environ.get("MAGICDEC_HOST_READ_SPIN", "1") != "0"
 
 
-def _sync(t):
-    if t.is_cuda:
-        torch.cuda.synchronize(t.device)
+def _sync(device):
+    if torch.device(device).type == "cuda":
+        torch.cuda.synchronize(device)
 
 
 def _read_flags(st: LoopState, collectives=()):
@@ -122,19 +122,14 @@ class PhaseTimers:
         self.draft = self.target = self.verify_loop = 0.0
 
     def start(self):
-        _sync_dev(self.device)
+        _sync(self.device)
         self._t = time.time()
 
     def lap(self, what):
-        _sync_dev(self.device)
+        _sync(self.device)
         now = time.time()
         setattr(self, what, getattr(self, what) + now - self._t)
         self._t = now
-
-
-def _sync_dev(device):
-    if torch.device(device).type == "cuda":
-        torch.cuda.synchronize(device)
 
 
 def warn_on_page_overflow(where):
@@ -182,6 +177,40 @@ def _iterate(engine, draft, st: LoopState, body, forced):
     return _read_flags(st, _collectives_of(engine, draft))
 
 
+def _spec_iteration(engine, draft, st: LoopState, gamma, eot_1, eot_2, max_nodes, next_double, forced_accept, timers,
+                    sampler, *, draft_step, verify, draft_lens, two_token_step, draft_back, bcast=None):
+    """The one speculative iteration: gamma draft steps, one verify, the fused accept/rollback, the one host read.
+    Returns (terminal, next_double).  The callers state what differs between the reference's loops:
+    draft_step(ids, cachelen_update) is one draft step (None: this rank does not draft), verify(tokens_buffer) the
+    target step, draft_lens() the draft's (cachelens, last_page_len) the accept kernel rolls back by `draft_back` -- read
+    after the steps ran; two_token_step says whether an all-accept iteration is followed by a two-token draft step."""
+    def body(forced):
+        if timers is not None:
+            timers.start()
+        if draft_step is not None:
+            _draft_round(draft_step, st, gamma, next_double and two_token_step, sampler if two_token_step else None)
+        if bcast is not None:
+            import torch.distributed as dist
+            dist.broadcast(st.tokens_buffer, src=bcast[0], group=bcast[1])
+        if timers is not None:
+            timers.lap("draft")
+        target_tokens = verify(st.tokens_buffer)
+        if timers is not None:
+            timers.lap("target")
+        if forced is not None:
+            target_tokens = _force_accept(st.tokens_buffer, target_tokens, forced, gamma)
+        draft_cachelens, draft_last_page_len = draft_lens()
+        double_buffer, cachelens_update = (st.double_buffer, st.cachelens_update) if two_token_step else (None, None)
+        ops.accept_rollback(st.tokens_buffer, target_tokens, st.output, st.num_nodes, engine.cachelens,
+                            engine.paged_kv_last_page_len, draft_cachelens, draft_last_page_len, gamma, draft_back,
+                            draft_back, eot_1, eot_2, max_nodes, st.accept_nums, st.bonus, double_buffer,
+                            cachelens_update, st.flags)
+    res = _iterate(engine, draft, st, body, forced_accept)
+    if timers is not None:
+        timers.lap("verify_loop")
+    return res
+
+
 def longspec_iteration(engine, draft, st: LoopState, gamma, eot_1, eot_2, max_nodes, next_double,
                        forced_accept=None, bcast=None, timers: PhaseTimers = None, sampler=None):
     """One iteration of the longspec loop: gamma draft steps, one verify, the fused accept/rollback.
@@ -189,65 +218,27 @@ def longspec_iteration(engine, draft, st: LoopState, gamma, eot_1, eot_2, max_no
 
     Tensor parallel (tests/SnapKV/longspec_benchmark.py:163-189): `draft` is None on ranks outside the draft
     sub-group; when the draft group is smaller than the target group the gamma draft tokens are broadcast from
-    `bcast = (src_rank, group)` before the verify.  Every rank runs the (replicated, all-integer) accept kernel."""
-    def body(forced):
-        if timers is not None:
-            timers.start()
-        if draft is not None:
-            _draft_round(lambda ids, cu: draft.inference(ids, cachelen_update=cu), st, gamma, next_double, sampler)
-        if bcast is not None:
-            import torch.distributed as dist
-            dist.broadcast(st.tokens_buffer, src=bcast[0], group=bcast[1])
-        if timers is not None:
-            timers.lap("draft")
-        target_tokens = engine.inference(st.tokens_buffer)
-        if timers is not None:
-            timers.lap("target")
-        if forced is not None:
-            target_tokens = _force_accept(st.tokens_buffer, target_tokens, forced, gamma)
-        ops.accept_rollback(st.tokens_buffer, target_tokens, st.output, st.num_nodes, engine.cachelens,
-                            engine.paged_kv_last_page_len, draft.cachelens if draft is not None else None,
-                            draft.paged_kv_last_page_len if draft is not None else None, gamma,
-                            gamma, gamma, eot_1, eot_2, max_nodes, st.accept_nums, st.bonus, st.double_buffer,
-                            st.cachelens_update, st.flags)
-    res = _iterate(engine, draft, st, body, forced_accept)
-    if timers is not None:
-        timers.lap("verify_loop")
-    return res
+    `bcast = (src_rank, group)` before the verify.  Every rank runs the (replicated, all-integer) accept kernel --
+    on `draft.paged_kv_last_page_len`, the reference's quirk (module docstring)."""
+    return _spec_iteration(
+        engine, draft, st, gamma, eot_1, eot_2, max_nodes, next_double, forced_accept, timers, sampler,
+        draft_step=None if draft is None else lambda ids, cu: draft.inference(ids, cachelen_update=cu),
+        verify=engine.inference,
+        draft_lens=lambda: (None, None) if draft is None else (draft.cachelens, draft.paged_kv_last_page_len),
+        two_token_step=True, draft_back=gamma, bcast=bcast)
 
 
 def selfspec_iteration(engine, st: LoopState, gamma, eot_1, eot_2, max_nodes, next_double, streaming,
                        forced_accept=None, timers: PhaseTimers = None, sampler=None):
     """One iteration of tests/SnapKV/selfspec_benchmark.py:121-211 (streaming=False: draft rolled back by
     gamma+1 and advanced by accept_nums, no two-token step) or tests/StreamingLLM/selfspec_benchmark.py:121-238."""
-    def body(forced):
-        if timers is not None:
-            timers.start()
-        if streaming:
-            _draft_round(lambda ids, cu: engine.speculate(ids, cachelen_update=cu), st, gamma, next_double, sampler)
-        else:
-            _draft_round(lambda ids, cu: engine.speculate(ids), st, gamma, False)
-        if timers is not None:
-            timers.lap("draft")
-        target_tokens = engine.verify(st.tokens_buffer)
-        if timers is not None:
-            timers.lap("target")
-        if forced is not None:
-            target_tokens = _force_accept(st.tokens_buffer, target_tokens, forced, gamma)
-        if streaming:
-            ops.accept_rollback(st.tokens_buffer, target_tokens, st.output, st.num_nodes, engine.cachelens,
-                                engine.paged_kv_last_page_len, engine.draft_cachelens,
-                                engine.draft_paged_kv_last_page_len, gamma, gamma, gamma, eot_1, eot_2, max_nodes,
-                                st.accept_nums, st.bonus, st.double_buffer, st.cachelens_update, st.flags)
-        else:
-            ops.accept_rollback(st.tokens_buffer, target_tokens, st.output, st.num_nodes, engine.cachelens,
-                                engine.paged_kv_last_page_len, engine.draft_cachelens,
-                                engine.draft_paged_kv_last_page_len, gamma, gamma + 1, gamma + 1, eot_1, eot_2,
-                                max_nodes, st.accept_nums, st.bonus, None, None, st.flags)
-    res = _iterate(engine, None, st, body, forced_accept)
-    if timers is not None:
-        timers.lap("verify_loop")
-    return res
+    return _spec_iteration(
+        engine, None, st, gamma, eot_1, eot_2, max_nodes, next_double, forced_accept, timers, sampler,
+        draft_step=((lambda ids, cu: engine.speculate(ids, cachelen_update=cu)) if streaming
+                    else (lambda ids, cu: engine.speculate(ids))),
+        verify=engine.verify,
+        draft_lens=lambda: (engine.draft_cachelens, engine.draft_paged_kv_last_page_len),
+        two_token_step=streaming, draft_back=gamma if streaming else gamma + 1)
 
 
 def _force_accept(tokens_buffer, target_tokens, forced_accept, gamma):
@@ -262,60 +253,57 @@ def _force_accept(tokens_buffer, target_tokens, forced_accept, gamma):
     return tt
 
 
-def run_longspec_batch(engine, draft, input_ids, gamma, max_len, eot_1, eot_2, forced_accept_fn=None,
-                       trace_fn=None, bcast=None, barrier=None, timers: PhaseTimers = None, sampler=None):
-    """A whole batch: prefill both models, loop until termination.  Returns (state, seconds in the loop).
-    sampler (Engine/sampling.Sampler, shared by target and draft): temperature / top-p speculative sampling instead of
-    greedy decoding; None (default) is the greedy loop."""
+def _run_spec_batch(engine, draft, input_ids, gamma, max_len, iteration, draft_prefill, barrier, label,
+                    forced_accept_fn, trace_fn, sampler):
+    """A whole speculative batch: prefill, loop until termination.  Returns (state, seconds in the loop).
+    iteration(st, next_double, forced_accept) is one of the two iteration wrappers above, draft_prefill(input_ids) the
+    draft-side prefill (None: there is none)."""
     B, S = input_ids.shape
     sampling.attach(engine, sampler)
     sampling.attach(draft, sampler)
     st = new_state(B, gamma, max_len + 1, input_ids.device, input_ids)
     st.tokens_buffer[:, :1] = engine.encode(input_ids=input_ids)[:, -1:]
-    if draft is not None:
-        draft.encode(input_ids=input_ids)
+    if draft_prefill is not None:
+        draft_prefill(input_ids=input_ids)
     if barrier is not None:
         barrier()
-    _sync(input_ids)
+    _sync(input_ids.device)
     t0 = time.perf_counter()
     terminal, nd = False, False
     while not terminal:
         fa = forced_accept_fn(st) if forced_accept_fn is not None else None
-        terminal, nd = longspec_iteration(engine, draft, st, gamma, eot_1, eot_2, S + 80, nd, fa, bcast, timers,
-                                          sampler)
+        terminal, nd = iteration(st, nd, fa)
         if trace_fn is not None:
             trace_fn(st)
-    _sync(input_ids)
+    _sync(input_ids.device)
     dt = time.perf_counter() - t0
     if input_ids.is_cuda:
-        warn_on_page_overflow("longspec batch")
+        warn_on_page_overflow(label)
         check_collectives(engine, draft)
     return st, dt
 
 
+def run_longspec_batch(engine, draft, input_ids, gamma, max_len, eot_1, eot_2, forced_accept_fn=None,
+                       trace_fn=None, bcast=None, barrier=None, timers: PhaseTimers = None, sampler=None):
+    """A whole batch: prefill both models, loop until termination.  Returns (state, seconds in the loop).
+    sampler (Engine/sampling.Sampler, shared by target and draft): temperature / top-p speculative sampling instead of
+    greedy decoding; None (default) is the greedy loop."""
+    max_nodes = input_ids.shape[1] + 80
+    return _run_spec_batch(
+        engine, draft, input_ids, gamma, max_len,
+        lambda st, nd, fa: longspec_iteration(engine, draft, st, gamma, eot_1, eot_2, max_nodes, nd, fa, bcast, timers,
+                                              sampler),
+        draft.encode if draft is not None else None, barrier, "longspec batch", forced_accept_fn, trace_fn, sampler)
+
+
 def run_selfspec_batch(engine, input_ids, gamma, max_len, eot_1, eot_2, streaming, forced_accept_fn=None,
                        trace_fn=None, timers: PhaseTimers = None, sampler=None):
-    B, S = input_ids.shape
-    sampling.attach(engine, sampler)
-    st = new_state(B, gamma, max_len + 1, input_ids.device, input_ids)
-    st.tokens_buffer[:, :1] = engine.encode(input_ids=input_ids)[:, -1:]
-    if streaming:
-        engine.draft_encode(input_ids=input_ids)
-    _sync(input_ids)
-    t0 = time.perf_counter()
-    terminal, nd = False, False
-    while not terminal:
-        fa = forced_accept_fn(st) if forced_accept_fn is not None else None
-        terminal, nd = selfspec_iteration(engine, st, gamma, eot_1, eot_2, S + 80, nd, streaming, fa, timers,
-                                          sampler)
-        if trace_fn is not None:
-            trace_fn(st)
-    _sync(input_ids)
-    dt = time.perf_counter() - t0
-    if input_ids.is_cuda:
-        warn_on_page_overflow("selfspec batch")
-        check_collectives(engine)
-    return st, dt
+    max_nodes = input_ids.shape[1] + 80
+    return _run_spec_batch(
+        engine, None, input_ids, gamma, max_len,
+        lambda st, nd, fa: selfspec_iteration(engine, st, gamma, eot_1, eot_2, max_nodes, nd, streaming, fa, timers,
+                                              sampler),
+        engine.draft_encode if streaming else None, None, "selfspec batch", forced_accept_fn, trace_fn, sampler)
 
 
 def run_baseline_batch(engine, input_ids, max_len, eot_1, eot_2, check_eot_every=1, sampler=None):
@@ -324,7 +312,7 @@ def run_baseline_batch(engine, input_ids, max_len, eot_1, eot_2, check_eot_every
     output = input_ids.clone()
     next_tokens = engine.encode(input_ids=input_ids)[:, -1:]
     output = torch.cat((output, next_tokens), dim=-1)
-    _sync(input_ids)
+    _sync(input_ids.device)
     t0 = time.perf_counter()
     steps = 0
     terminate = False
@@ -335,7 +323,7 @@ def run_baseline_batch(engine, input_ids, max_len, eot_1, eot_2, check_eot_every
         if steps % check_eot_every == 0:
             last = next_tokens[:, -1]
             terminate = bool(((last == eot_1) | (last == eot_2)).any())
-    _sync(input_ids)
+    _sync(input_ids.device)
     dt = time.perf_counter() - t0
     if input_ids.is_cuda:
         warn_on_page_overflow("baseline batch")

@@ -1631,6 +1631,27 @@ def test_iteration_hook_runs_after_the_body_and_before_the_host_read():
     assert harness._iterate(None, None, st, lambda f: None, None) == (False, False)
 
 
+def test_harness_public_signatures_are_the_ones_callers_use_positionally():
+    """bench.py, __graft_entry__.py and tools/backend_step_trace.py call the iteration functions positionally and the
+    tests and workers call the batch runners by these keyword names: parameter names, order and defaults are pinned."""
+    import inspect
+    from magicdec_amd import harness
+    want = {
+        "new_state": "(B, gamma, out_cols, device, input_ids=None)",
+        "longspec_iteration": "(engine, draft, st: 'LoopState', gamma, eot_1, eot_2, max_nodes, next_double, "
+                              "forced_accept=None, bcast=None, timers: 'PhaseTimers' = None, sampler=None)",
+        "selfspec_iteration": "(engine, st: 'LoopState', gamma, eot_1, eot_2, max_nodes, next_double, streaming, "
+                              "forced_accept=None, timers: 'PhaseTimers' = None, sampler=None)",
+        "run_longspec_batch": "(engine, draft, input_ids, gamma, max_len, eot_1, eot_2, forced_accept_fn=None, "
+                              "trace_fn=None, bcast=None, barrier=None, timers: 'PhaseTimers' = None, sampler=None)",
+        "run_selfspec_batch": "(engine, input_ids, gamma, max_len, eot_1, eot_2, streaming, forced_accept_fn=None, "
+                              "trace_fn=None, timers: 'PhaseTimers' = None, sampler=None)",
+        "run_baseline_batch": "(engine, input_ids, max_len, eot_1, eot_2, check_eot_every=1, sampler=None)",
+    }
+    for name, sig in want.items():
+        assert str(inspect.signature(getattr(harness, name))) == sig, name
+
+
 def test_one_resident_copy_per_weight_release_and_restore():
     """every weight a hand-written kernel may serve used to be held TWICE (streaming layout +
     row-major: 16.9 GB at configs[2]).  Now (a) only weights that some step of THIS engine runs on a hand-written kernel
