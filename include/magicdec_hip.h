@@ -418,7 +418,9 @@ int md_accept_rollback(int64_t* tokens_buffer, const int64_t* target_tokens, int
  * K11  temperature / top-p sampling and lossless speculative sampling
  *     reference: Engine/utils.py:68-98 (get_sampling_logits / sample: temperature + top-p filter, multinomial draw;
  *     cuda_graph_for_target_sample :122-149).  The reference never wires them into a speculative loop; here they
- *     replace the argmax of every decode loop when a temperature > 0 is asked for (TP = 1 only).
+ *     replace the argmax of every decode loop when a temperature > 0 is asked for: md_sample_rows /
+ *     md_spec_verify_sample on one GPU, the md_*_shard_* phases below when the lm head is vocab-sharded (tensor
+ *     parallelism) -- same semantics, same bits.
  * Semantics.  l = a row of bf16 logits, T > 0, invT = fp32(1 / T), m = max(l).
  *   key(l_v)   order-preserving 16-bit key of the bf16 bit pattern: bits | 0x8000 if the sign is clear, ~bits
  *              otherwise (a larger key is a larger logit; -0 sorts just below +0).
@@ -457,6 +459,43 @@ int md_accept_rollback(int64_t* tokens_buffer, const int64_t* target_tokens, int
  *   stored only if j < gamma).
  * md_spec_verify_sample: stats of the B*(gamma+1) target rows into target_stats (workspace [B*(gamma+1)]), then the
  *   verify above; advances the iteration counter (and resets the step).
+ * Sharded form (tensor parallelism, the lm head chunked by vocabulary).  A rank holds the columns [vocab_offset,
+ *   vocab_offset + v_loc) of every row (v_loc may differ per rank, vocab_offset need not be a multiple of anything, rows
+ *   may be unaligned); the ranks' column ranges tile [0, vocab_total).  Every quantity above is a max, an integer sum
+ *   or an argmax with a total order, and the noise is keyed by the GLOBAL vocab index, so the phases below, with one
+ *   all-reduce of a small int64 device tensor between two launches, give the stats, jr and tokens of the one-GPU
+ *   entry points on the concatenated row, bit for bit, identically on every rank.  Nothing is read back to the host.
+ *   Rows: a draw has R = B (row row_sel[b]-1 / the last of n, as md_sample_rows); a verify has R = B (gamma+1), n = 1.
+ *   A. md_sample_shard_max    red[r] = key(max of the shard of row r) (-inf throughout: key(-inf)).  With
+ *                             tokens_buffer (verify): red[R + b gamma + j] = 1 << 32 | target bits at d << 16 | ring bits
+ *                             at d, written by the rank whose columns hold d = tokens_buffer[b, j+1], else 0; a d outside
+ *                             [0, vocab_total) has no owner.                                       all-reduce MAX
+ *   B. md_sample_shard_hist   (hist_hi = NULL) hist[r, 256] = sum of w_v by the key's high byte, under the global m
+ *                             decoded from red.                                                    all-reduce SUM
+ *   C. md_sample_shard_hist   (hist_hi = the reduced B; top_p < 1 only) every workgroup re-derives Z, hb, above_hb from
+ *                             the reduced row, then hist[r, 256] = sum of w_v by the low byte inside bin hb (zeros if the
+ *                             shard has no mass there).                                            all-reduce SUM
+ *   D. md_sample_shard_draw   stats from the reduced histograms (written to ring_stats[b, j] in draft mode, as above;
+ *                             the local columns go to the rank's ring shard [B, gamma, v_loc]); cand[b] = the shard's
+ *                             Gumbel-max winner.
+ *      md_spec_verify_shard   target_stats of all B (gamma+1) rows; the accept walk from the probes; cand[b] = {the
+ *                             shard's residual winner at jr (or bonus winner if jr = gamma), its fallback winner
+ *                             (p~_jr without d), jr}.  The ring is read at ring + (b gamma + j) ring_row_stride +
+ *                             ring_col_offset + local column: a ring shard (stride v_loc, offset 0) or this rank's
+ *                             columns of a full ring (stride vocab_total, offset vocab_offset).      all-reduce MAX
+ *      A candidate is an int64 whose signed order is (score ascending, global index descending): the score's fp32
+ *      bits (-0 as +0) mapped to an ordered uint32 u, value u << 31 | (0x7fffffff - v); "none" (nothing kept, or a best
+ *      of -inf) is -1, below every candidate.  MAX over ranks is the one-GPU argmax.
+ *   E. md_sample_shard_finish / md_spec_verify_shard_finish   tokens_out / target_tokens in the encoding above, with
+ *                             the last-resort rules on the global result (no residual candidate anywhere: the fallback;
+ *                             none either: d == 0 ? 1 : 0; a draw with nothing kept: token 0).  Only this phase advances
+ *                             the counters, so every phase of a call reads the same iteration and step.
+ *   Collectives per logical call: 4 (top_p < 1) or 3 (top_p = 1), for a draw and for a verify alike.
+ *   One corner is outside the bit-for-bit claim: a row whose maximum is a zero present with both signs.  The reduced
+ *   key orders -0 below +0, so the sharded m is +0; the one-GPU fmaxf may return either zero.  Only the sign bit of
+ *   the stored md_sample_stats.m can differ; l - m, every mass and every token are the same.
+ *   Status: validated bit for bit against the one-GPU entry points with the ranks emulated in one process on one GPU,
+ *   and as two processes sharing one GPU over gloo (tests/test_gpu_sampling_tp.py); it has not run across physical GPUs.
  * md_philox4x32_10_host: out[i] = Philox4x32-10(ctr[i], {key0, key1}) for n counters of 4 words (host memory). Host.
  * ---------------------------------------------------------------------- */
 #define MD_SAMPLE_PREFILL 0
@@ -483,6 +522,31 @@ int md_spec_verify_sample(const void* logits, int64_t row_stride, int B, int gam
                           float top_p, uint64_t seed, const int64_t* tokens_buffer /* [B,gamma+1] */,
                           const void* ring, const void* ring_stats, void* target_stats /* [B*(gamma+1)] */,
                           int32_t* counters, int64_t* target_tokens /* [B,gamma+1] */, md_stream_t stream);
+int md_sample_shard_max(const void* logits, int64_t row_stride, int R, int n, int v_loc,
+                        const int64_t* row_sel /* [R] or NULL */, const int64_t* tokens_buffer /* verify, or NULL */,
+                        const void* ring, int64_t ring_row_stride, int64_t ring_col_offset, int gamma, int vocab_offset,
+                        int vocab_total, int64_t* red_out /* [R] (+ [B,gamma] probes) */, md_stream_t stream);
+int md_sample_shard_hist(const void* logits, int64_t row_stride, int R, int n, int v_loc, const int64_t* row_sel,
+                         float temperature, float top_p, const int64_t* red_max /* reduced */,
+                         const int64_t* hist_hi /* reduced [R,256]: phase C; NULL: phase B */,
+                         int64_t* hist_out /* [R,256] */, md_stream_t stream);
+int md_sample_shard_draw(const void* logits, int64_t row_stride, int B, int n, int v_loc, int vocab_offset,
+                         int vocab_total, float temperature, float top_p, uint64_t seed, int purpose,
+                         const int64_t* row_sel, const int32_t* counters, const int64_t* red_max,
+                         const int64_t* hist_hi, const int64_t* hist_lo /* NULL iff top_p == 1 */,
+                         void* ring /* [B,gamma,v_loc] bf16 or NULL */, void* ring_stats, int gamma,
+                         int64_t* cand_out /* [B] */, md_stream_t stream);
+int md_sample_shard_finish(const int64_t* cand /* reduced [B] */, int B, int n, int32_t* counters, int advance,
+                           int64_t* tokens_out /* [B,n] */, md_stream_t stream);
+int md_spec_verify_shard(const void* logits, int64_t row_stride, int B, int gamma, int v_loc, int vocab_offset,
+                         int vocab_total, float temperature, float top_p, uint64_t seed,
+                         const int64_t* tokens_buffer, const void* ring, int64_t ring_row_stride,
+                         int64_t ring_col_offset, const void* ring_stats, const int64_t* red_max /* reduced */,
+                         const int64_t* hist_hi, const int64_t* hist_lo /* NULL iff top_p == 1 */,
+                         void* target_stats /* [B*(gamma+1)] */, const int32_t* counters,
+                         int64_t* cand_out /* [B,3] */, md_stream_t stream);
+int md_spec_verify_shard_finish(const int64_t* cand /* reduced [B,3] */, const int64_t* tokens_buffer, int B, int gamma,
+                                int32_t* counters, int64_t* target_tokens /* [B,gamma+1] */, md_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * C1  the per-layer sum-all-reduce of the tensor-parallel decode path over xGMI peer-mapped buffers

@@ -11,11 +11,18 @@ to the role its back-end set for the step:
 
 Everything the kernels read lives here, allocated once, before any graph capture: the iteration counter and the
 draft-step index are device tensors the kernels advance themselves, so one captured graph per step serves every
-iteration.  TP = 1 only; one temperature / top_p per run (changing them after a capture needs clear_graphs()).
+iteration.  One temperature / top_p per run (changing them after a capture needs clear_graphs()).
+
+Sampler is the one-GPU form and rejects tensor-parallel models.  ShardedSampler is the opt-in form for a vocab-sharded
+lm head (Engine/tp.py:apply_tp): the same semantics and the same bits, as a chain of local launches with one small
+all-reduce between two of them (K11 "sharded": 4 collectives per call, 3 at top_p = 1).  The phases are validated with
+the ranks emulated in one process on one GPU, the class by two processes sharing one GPU over gloo
+(tests/test_gpu_sampling_tp.py); nothing here has run across physical GPUs.
 """
 from __future__ import annotations
 
 import torch
+import torch.distributed as dist
 
 from .. import ops
 
@@ -92,6 +99,140 @@ class Sampler:
             purpose = ops.SAMPLE_PREFILL if role == "prefill" else ops.SAMPLE_BASELINE
             return ops.sample_rows(logits, n, T, p, s, purpose, self.counters, ops.ADVANCE_ITER)
         raise ValueError(f"sampling: step role {role!r} is not one of {ROLES}")
+
+
+def shard_offsets(widths):
+    """Exclusive prefix sum of the ranks' local vocabulary widths -> (offsets, total).  The widths need not be equal:
+    torch.chunk (Engine/tp.py) gives the last rank fewer columns."""
+    offs, tot = [], 0
+    for w in widths:
+        if w < 1:
+            raise ValueError(f"sharded sampling: a rank holds no vocabulary columns (widths {list(widths)})")
+        offs.append(tot)
+        tot += int(w)
+    return offs, tot
+
+
+def _group_ranks(group):
+    """The global ranks of `group`, or None when this rank is outside it (torch raises ValueError / KeyError)."""
+    try:
+        return tuple(dist.get_process_group_ranks(group))
+    except (ValueError, KeyError, RuntimeError, TypeError, AttributeError):
+        return None
+
+
+def _same_ranks(a, b):
+    ra, rb = _group_ranks(a), _group_ranks(b)
+    return ra is not None and ra == rb          # a group this rank cannot see matches nothing
+
+
+class ShardedSampler(Sampler):
+    """Sampler for a model whose lm head is vocab-sharded over `group`: rank r holds the logits columns
+    [vocab_offset, vocab_offset + v_loc).  head() runs launch -> all_reduce(MAX | SUM) -> launch ... on device tensors
+    allocated here; nothing is read back to the host (the returned token tensor is the only per-step allocation, as in
+    the base class).
+
+    The draft of a longspec run is either sharded over the same ranks as the target (ring shard [B, gamma, v_loc]) or,
+    with replicate_draft, whole on every rank (full ring [B, gamma, vocab], drawn by the one-GPU md_sample_rows, which
+    is bit-identical on every rank).  A draft sharded over a sub-group of the target's ranks is NOT supported: the ranks
+    outside the sub-group have no ring to verify against (it would have to be all-gathered to them)."""
+
+    def __init__(self, temperature, top_p, seed, B, gamma, v_loc, device, group, replicate_draft=False):
+        self.group = group
+        dev = torch.device(device)
+        self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
+        mine = torch.tensor([v_loc], dtype=torch.int64, device=dev)
+        parts = [torch.zeros_like(mine) for _ in range(self.world)]
+        dist.all_gather(parts, mine, group=group)
+        widths = [int(t.item()) for t in parts]
+        offs, total = shard_offsets(widths)
+        if widths[self.rank] != v_loc:
+            raise ValueError(f"sharded sampling: rank {self.rank} holds {v_loc} columns, the group says {widths[self.rank]}")
+        self.v_loc, self.vocab_offset, self.vocab_total = int(v_loc), offs[self.rank], total
+        self.replicate_draft = bool(replicate_draft)
+        super().__init__(temperature, top_p, seed, B, gamma, total if replicate_draft else v_loc, device)
+        self.vocab = total
+        g = max(gamma, 1)
+        i64 = dict(dtype=torch.int64, device=dev)
+        R = B * (g + 1)
+        # reduction buffers: a set for the draws (B rows) and one for the verify (B (gamma+1) rows + B gamma probes)
+        self._draw = dict(red=torch.zeros(B, **i64), hi=torch.zeros((B, ops.HIST_BINS), **i64),
+                          lo=torch.zeros((B, ops.HIST_BINS), **i64), cand=torch.zeros(B, **i64))
+        self._verify = dict(red=torch.zeros(R + B * g, **i64), hi=torch.zeros((R, ops.HIST_BINS), **i64),
+                            lo=torch.zeros((R, ops.HIST_BINS), **i64), cand=torch.zeros((B, ops.CAND_WORDS), **i64))
+
+    def check_model(self, model):
+        grp = getattr(model, "process_group", None)
+        width = model.output.weight.shape[0]
+        if grp is None:
+            if not self.replicate_draft:
+                raise ValueError("sharded sampling: the model is not tensor-parallel (an unsharded draft next to a sharded "
+                                 "target needs replicate_draft=True; a one-GPU run takes the plain Sampler)")
+            if width != self.vocab_total:
+                raise ValueError(f"sharded sampling: the replicated draft's vocabulary ({width}) differs from the target's "
+                                 f"({self.vocab_total})")
+            return
+        if grp is not self.group and not _same_ranks(grp, self.group):
+            raise ValueError("sharded sampling: the model is sharded over another group of ranks than the sampler's "
+                             f"({_group_ranks(grp)} vs {_group_ranks(self.group)}).  A draft sharded over a sub-group of the "
+                             "target's ranks is not supported: the other ranks would have no draft ring to verify against")
+        if width != self.v_loc:
+            raise ValueError(f"sharded sampling: the model's local head width ({width}) differs from the sampler's "
+                             f"({self.v_loc}); draft and target must shard equal vocabularies alike")
+
+    def _reduce(self, t, op):
+        dist.all_reduce(t, op=op, group=self.group)
+
+    def _filter(self, logits, n, bufs, row_sel=None, tokens_buffer=None, ring=None, ring_col_offset=0):
+        """Phases A-C: after it bufs holds the reduced max (+ probes) and histograms of the drawn rows."""
+        T, p = self.temperature, self.top_p
+        ops.shard_max(logits, n, self.vocab_offset, self.vocab_total, bufs["red"], row_sel=row_sel,
+                      tokens_buffer=tokens_buffer, ring=ring, ring_col_offset=ring_col_offset)
+        self._reduce(bufs["red"], dist.ReduceOp.MAX)
+        ops.shard_hist(logits, n, T, p, bufs["red"], bufs["hi"], row_sel=row_sel)
+        self._reduce(bufs["hi"], dist.ReduceOp.SUM)
+        if p < 1:
+            ops.shard_hist(logits, n, T, p, bufs["red"], bufs["lo"], hist_hi=bufs["hi"], row_sel=row_sel)
+            self._reduce(bufs["lo"], dist.ReduceOp.SUM)
+            return bufs["lo"]
+        return None
+
+    def head(self, logits, role, idx, B, n):
+        T, p, s = self.temperature, self.top_p, self.seed
+        if logits.shape[1] != self.v_loc:
+            if role in ("draft", "prefill") and self.replicate_draft and logits.shape[1] == self.vocab_total:
+                # the replicated draft (its prefill and its steps) holds whole rows on every rank: the one-GPU draw,
+                # identical everywhere, counters included
+                return super().head(logits, role, idx, B, n)
+            raise ValueError(f"sharded sampling: {role} logits of width {logits.shape[1]}, this rank's is {self.v_loc}")
+        if B != self.B:
+            raise ValueError(f"sharded sampling: step of {B} requests, the sampler was built for {self.B}")
+        if role == "verify":
+            if n != self.gamma + 1:
+                raise ValueError(f"verify step with {n} rows per request, sampler gamma = {self.gamma}")
+            bufs = self._verify
+            off = self.vocab_offset if self.replicate_draft else 0
+            lo = self._filter(logits, 1, bufs, tokens_buffer=idx, ring=self.ring, ring_col_offset=off)
+            ops.spec_verify_shard(logits, idx, self.vocab_offset, self.vocab_total, self.ring, self.ring_stats,
+                                  bufs["red"], bufs["hi"], lo, self.target_stats, self.counters, T, p, s, bufs["cand"],
+                                  ring_col_offset=off)
+            self._reduce(bufs["cand"], dist.ReduceOp.MAX)
+            return ops.spec_verify_shard_finish(bufs["cand"], idx, self.counters)
+        if role == "draft":
+            purpose, advance, draft = ops.SAMPLE_DRAFT, ops.ADVANCE_STEP, True
+        elif role in ("prefill", "baseline"):
+            purpose = ops.SAMPLE_PREFILL if role == "prefill" else ops.SAMPLE_BASELINE
+            advance, draft = ops.ADVANCE_ITER, False
+        else:
+            raise ValueError(f"sampling: step role {role!r} is not one of {ROLES}")
+        bufs = self._draw
+        row_sel = self.row_sel if (draft and n == 2) else None
+        lo = self._filter(logits, n, bufs, row_sel=row_sel)
+        ops.shard_draw(logits, n, self.vocab_offset, self.vocab_total, T, p, s, purpose, self.counters, bufs["red"],
+                       bufs["hi"], lo, bufs["cand"], row_sel=row_sel, ring=self.ring if draft else None,
+                       ring_stats=self.ring_stats if draft else None)
+        self._reduce(bufs["cand"], dist.ReduceOp.MAX)
+        return ops.shard_finish(bufs["cand"], n, self.counters, advance)
 
 
 def attach(backend, sampler):

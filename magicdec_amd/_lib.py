@@ -87,6 +87,13 @@ _SIGNATURES = {
     "md_philox4x32_10_host": (c_int, [P, I, c_uint32, c_uint32, P]),
     "md_sample_rows": (c_int, [P, L, I, I, I, c_float, c_float, c_uint64, I, P, P, I, P, P, I, P, P]),
     "md_spec_verify_sample": (c_int, [P, L, I, I, I, c_float, c_float, c_uint64, P, P, P, P, P, P, P]),
+    "md_sample_shard_max": (c_int, [P, L, I, I, I, P, P, P, L, L, I, I, I, P, P]),
+    "md_sample_shard_hist": (c_int, [P, L, I, I, I, P, c_float, c_float, P, P, P, P]),
+    "md_sample_shard_draw": (c_int, [P, L, I, I, I, I, I, c_float, c_float, c_uint64, I, P, P, P, P, P, P, P, I, P, P]),
+    "md_sample_shard_finish": (c_int, [P, I, I, P, I, P, P]),
+    "md_spec_verify_shard": (c_int, [P, L, I, I, I, I, I, c_float, c_float, c_uint64, P, P, L, L, P, P, P, P, P, P, P,
+                                     P]),
+    "md_spec_verify_shard_finish": (c_int, [P, P, I, I, P, P, P]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -90,8 +90,13 @@ def add_sampling_args(parser):
     functions above reproduce exactly): temperature 0 (the default) is the greedy loop, unchanged; > 0 samples with the
     tempered top-p filter and lossless speculative sampling (Engine/sampling.py), seeded by --seed."""
     parser.add_argument('--temperature', type=float, default=0.0,
-                        help='Sampling temperature; 0 = greedy decoding (default).  TP = 1 only.')
+                        help='Sampling temperature; 0 = greedy decoding (default).  One rank, unless '
+                             '--sharded_sampling is given.')
     parser.add_argument('--top_p', type=float, default=1.0, help='Top-p (nucleus) mass kept when sampling, in (0, 1].')
+    parser.add_argument('--sharded_sampling', action='store_true',
+                        help='allow --temperature > 0 with several ranks in --rank_group: the vocab-sharded sampler '
+                             '(Engine/sampling.ShardedSampler; same tokens as one GPU).  Opt-in: validated with ranks '
+                             'emulated on one GPU only, never across physical GPUs.')
     return parser
 
 
@@ -103,9 +108,17 @@ def parse_entry_args(parser, argv=None):
         parser.error(f"--temperature must be >= 0, got {args.temperature}")
     if not 0 < args.top_p <= 1:
         parser.error(f"--top_p must be in (0, 1], got {args.top_p}")
-    if args.temperature > 0 and args.rank_group is not None and len(args.rank_group) > 1:
+    several = args.rank_group is not None and len(args.rank_group) > 1
+    if args.temperature > 0 and several and not args.sharded_sampling:
         parser.error("--temperature > 0 supports one rank only (TP = 1): the vocab-sharded sampler needs cross-rank "
-                     "max / Z / histogram reductions and is not implemented")
+                     "max / Z / histogram reductions and is opt-in (--sharded_sampling)")
+    draft_ranks = getattr(args, "draft_rank_group", None)
+    if (args.sharded_sampling and args.temperature > 0 and several and draft_ranks is not None
+            and not getattr(args, "replicate_draft", False) and len(draft_ranks) != len(args.rank_group)):
+        parser.error(f"--sharded_sampling needs the draft on every target rank: --draft_rank_group has {len(draft_ranks)} "
+                     f"ranks, --rank_group {len(args.rank_group)}.  With the draft sharded over a sub-group, the other "
+                     "ranks hold no draft ring to verify against; give --draft_rank_group as many ranks as --rank_group, "
+                     "or --replicate_draft")
     return args
 
 
@@ -113,8 +126,13 @@ def _sampler(args, engine, gamma, device):
     """The run's Sampler (None for greedy decoding)."""
     if args.temperature == 0:
         return None
-    from .Engine.sampling import Sampler
-    return Sampler(args.temperature, args.top_p, args.seed, args.B, gamma, engine.model.output.weight.shape[0], device)
+    from .Engine.sampling import Sampler, ShardedSampler
+    width = engine.model.output.weight.shape[0]
+    group = getattr(engine.model, "process_group", None)
+    if group is not None and getattr(args, "sharded_sampling", False):
+        return ShardedSampler(args.temperature, args.top_p, args.seed, args.B, gamma, width, device, group,
+                              replicate_draft=bool(getattr(args, "replicate_draft", False)))
+    return Sampler(args.temperature, args.top_p, args.seed, args.B, gamma, width, device)
 
 
 def _eot(tokenizer):

@@ -489,6 +489,426 @@ __global__ __launch_bounds__(NT) void spec_verify_kernel(const VerifyParams p) {
 
 bool wide(int rows, int vocab) { return rows <= 512 && vocab >= 16384; }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Vocab-sharded form (tensor parallelism): a rank holds the columns [vocab_offset, vocab_offset + v_loc) of every row.
+// A logical call is a chain of launches with ONE all-reduce of a small int64 device tensor between two of them
+// (header, K11 "sharded"): max (+ verify probe) -> MAX, high-byte histogram -> SUM, low-byte histogram -> SUM
+// (top_p < 1 only), local candidates -> MAX, finish.  Every quantity that crosses ranks is an integer or an order key,
+// so the reduced values -- hence the stats, jr and the tokens -- are the bits of the one-GPU kernels on the whole row.
+
+// the inverse of key16
+__device__ __forceinline__ uint32_t bits_of_key16(uint32_t k) { return (k & 0x8000u) ? (k & 0x7fffu) : (~k & 0xffffu); }
+
+constexpr long long kNoCand = -1;
+// (score, global index) as an int64 whose signed order is (score ascending, index descending); -0 counts as +0, as in
+// the float compare of block_argmax.  63 bits: never negative, so kNoCand is below every candidate.
+__device__ __forceinline__ long long pack_cand(float sc, int v) {
+    if (v < 0) return kNoCand;
+    uint32_t u = __float_as_uint(sc);
+    if ((u << 1) == 0) u = 0;
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return (long long)(((unsigned long long)u << 31) | (unsigned long long)(0x7fffffff - v));
+}
+__device__ __forceinline__ int cand_index(long long c) { return 0x7fffffff - (int)(c & 0x7fffffffll); }
+
+// block_argmax that also returns the winning score: (best, bi) of the block in every thread, bi = -1 if best is -inf
+template <int NT>
+__device__ void block_argmax_sc(float& best, int& bi, Smem& s) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o);
+        const int oi = __shfl_xor(bi, o);
+        if (ov > best || (ov == best && oi < bi)) {
+            best = ov;
+            bi = oi;
+        }
+    }
+    const int wave = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        s.redf[wave] = best;
+        s.redi[wave] = bi;
+    }
+    __syncthreads();
+    best = s.redf[0];
+    bi = s.redi[0];
+    for (int w = 1; w < NT / 64; ++w)
+        if (s.redf[w] > best || (s.redf[w] == best && s.redi[w] < bi)) {
+            best = s.redf[w];
+            bi = s.redi[w];
+        }
+    if (best == -INFINITY) bi = -1;
+}
+
+// the drawn row of request b: row_sel[b] - 1 of its n rows, else the last
+__device__ __forceinline__ const unsigned short* shard_row(const unsigned short* logits, int64_t row_stride, int n,
+                                                           const int64_t* row_sel, int b) {
+    int r = n - 1;
+    if (row_sel) {
+        const int64_t q = row_sel[b] - 1;
+        r = q < 0 ? 0 : (q >= n ? n - 1 : (int)q);
+    }
+    return logits + ((int64_t)b * n + r) * row_stride;
+}
+
+// Stats of a row from its reduced quantities, as row_stats derives them from the row itself: Z from the high-byte
+// histogram, hb / above_hb by scan_select, then (unless only_hb) kstar and Z_kept from the low-byte histogram of bin hb.
+// Result in s.st (only_hb: s.sel = hb, s.above = above_hb; returns thr).
+__device__ double derive_stats(float mx, const long long* __restrict__ hi, const long long* __restrict__ lo,
+                               float top_p, bool only_hb, Smem& s) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) s.hist[i] = (unsigned long long)hi[i];
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        unsigned long long z = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) z += s.hist[4 * threadIdx.x + e];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o);
+        if (threadIdx.x == 0) {
+            s.above = z;
+            if (top_p >= 1.f) s.st = RowStats{mx, 0u, z};
+        }
+    }
+    __syncthreads();
+    if (top_p >= 1.f) return 0.0;
+    const unsigned long long Z = s.above;
+    const double thr = (double)top_p * (double)Z;
+    __syncthreads();
+    scan_select(s, 0ull, thr);
+    if (only_hb) return thr;
+    const int hb = s.sel;
+    const unsigned long long above_hb = s.above;
+    __syncthreads();
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) s.hist[i] = (unsigned long long)lo[i];
+    __syncthreads();
+    scan_select(s, above_hb, thr);
+    if (threadIdx.x == 0) s.st = RowStats{mx, ((uint32_t)hb << 8) | (uint32_t)s.sel, s.above + s.hist[s.sel]};
+    __syncthreads();
+    return thr;
+}
+
+struct ShardParams {
+    const unsigned short* logits;   // this rank's columns of [R*n, row_stride]
+    int64_t row_stride;
+    int R, n, v_loc, vocab_offset, vocab_total, gamma, purpose;
+    float invT, top_p;
+    uint64_t seed;
+    const int64_t* row_sel;
+    const int64_t* tokens_buffer;   // [B, gamma+1] (verify)
+    const unsigned short* ring;     // verify: row (b, j) at ring + (b*gamma + j) * ring_row_stride + ring_col_offset
+    int64_t ring_row_stride, ring_col_offset;
+    unsigned short* ring_out;       // draft: this rank's ring shard [B, gamma, v_loc]
+    RowStats* ring_stats;           // [B, gamma]
+    RowStats* target_stats;         // [B*(gamma+1)]
+    int32_t* counters;
+    const long long* red_max;       // reduced phase-A tensor
+    const long long* hist_hi;       // reduced [R, 256]
+    const long long* hist_lo;       // reduced [R, 256] (top_p < 1)
+    long long* out;                 // this phase's tensor to reduce
+};
+
+// phase A: key of the shard's max per row; verify: the probe of the draft token d of (b, j), written by its owner
+template <int NT>
+__global__ __launch_bounds__(NT) void shard_max_kernel(const ShardParams p) {
+    __shared__ Smem s;
+    const int row = blockIdx.x;
+    const unsigned short* lr = shard_row(p.logits, p.row_stride, p.n, p.row_sel, row);
+    float mx = -INFINITY;
+    for_row<NT>(lr, p.v_loc, [&](int, uint32_t b) { mx = fmaxf(mx, bf16_bits_to_f32(b)); });
+    mx = block_max<NT>(mx, s);
+    if (threadIdx.x == 0) {
+        p.out[row] = (long long)key16(__float_as_uint(mx) >> 16);
+        if (p.tokens_buffer) {
+            const int G = p.gamma, b = row / (G + 1), j = row % (G + 1);
+            if (j < G) {
+                const int64_t d = p.tokens_buffer[(int64_t)b * (G + 1) + j + 1];
+                long long probe = 0;
+                if (d >= 0 && d < p.vocab_total && d >= p.vocab_offset && d < (int64_t)p.vocab_offset + p.v_loc) {
+                    const int64_t c = d - p.vocab_offset;
+                    const unsigned short* rr = p.ring + ((int64_t)b * G + j) * p.ring_row_stride + p.ring_col_offset;
+                    probe = (1ll << 32) | ((long long)lr[c] << 16) | (long long)rr[c];
+                }
+                p.out[(int64_t)p.R + (int64_t)b * G + j] = probe;
+            }
+        }
+    }
+}
+
+// phase B (hist_hi == null): masses by the high byte of the key, under the global max; phase C: by the low byte inside
+// the bin hb that every rank derives from the reduced phase-B row
+template <int NT>
+__global__ __launch_bounds__(NT) void shard_hist_kernel(const ShardParams p) {
+    __shared__ Smem s;
+    const int row = blockIdx.x;
+    const unsigned short* lr = shard_row(p.logits, p.row_stride, p.n, p.row_sel, row);
+    const float mx = bf16_bits_to_f32((unsigned short)bits_of_key16((uint32_t)p.red_max[row]));
+    int hb = -1;
+    if (p.hist_hi) {
+        derive_stats(mx, p.hist_hi + (int64_t)row * 256, nullptr, p.top_p, true, s);
+        hb = s.sel;
+        __syncthreads();
+    }
+    for (int i = threadIdx.x; i < 256; i += NT) s.hist[i] = 0;
+    __syncthreads();
+    if (hb < 0) {
+        for_row<NT>(lr, p.v_loc, [&](int, uint32_t b) {
+            const unsigned long long w = mass_fx(bf16_bits_to_f32(b), mx, p.invT);
+            if (w) atomicAdd(&s.hist[key16(b) >> 8], w);
+        });
+    } else {
+        for_row<NT>(lr, p.v_loc, [&](int, uint32_t b) {
+            const uint32_t k = key16(b);
+            if ((int)(k >> 8) == hb) {
+                const unsigned long long w = mass_fx(bf16_bits_to_f32(b), mx, p.invT);
+                if (w) atomicAdd(&s.hist[k & 0xffu], w);
+            }
+        });
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < 256; i += NT) p.out[(int64_t)row * 256 + i] = (long long)s.hist[i];
+}
+
+// Gumbel-max over this shard's kept tokens, noise and index by the global v = voff + local; -> (best, bi) in every thread
+template <int NT>
+__device__ void draw_shard(const unsigned short* __restrict__ row, int v_loc, int voff, const RowStats& st, float invT,
+                           const NoiseKey& nk, Smem& s, unsigned short* __restrict__ copy_to, float& best, int& bi) {
+    best = -INFINITY;
+    bi = 0x7fffffff;
+    int grp = -1;
+    Word4 w{0, 0, 0, 0};
+    auto visit = [&](int vl, uint32_t b) {
+        if (key16(b) < st.kstar) return;
+        const int v = voff + vl;
+        if ((v >> 2) != grp) {
+            grp = v >> 2;
+            w = noise_block(nk, v);
+        }
+        const float sc = (bf16_bits_to_f32(b) - st.m) * invT + gumbel_of(pick(w, v));
+        if (sc > best || (sc == best && v < bi)) {
+            best = sc;
+            bi = v;
+        }
+    };
+    int start = 0;
+    if (((((uintptr_t)row) | (uintptr_t)copy_to) & 15) == 0) {
+        const int nvec = v_loc >> 3;
+        for (int i = threadIdx.x; i < nvec; i += NT) {
+            const u32x4 raw = reinterpret_cast<const u32x4*>(row)[i];
+            if (copy_to) reinterpret_cast<u32x4*>(copy_to)[i] = raw;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) visit(i * 8 + e, (raw[e >> 1] >> ((e & 1) * 16)) & 0xffffu);
+        }
+        start = nvec << 3;
+    }
+    for (int vl = start + threadIdx.x; vl < v_loc; vl += NT) {
+        const unsigned short b = row[vl];
+        if (copy_to) copy_to[vl] = b;
+        visit(vl, (uint32_t)b);
+    }
+    block_argmax_sc<NT>(best, bi, s);
+}
+
+// phase D of a draw: stats from the reduced histograms (identical on every rank), the local candidate, the ring shard
+template <int NT>
+__global__ __launch_bounds__(NT) void shard_draw_kernel(const ShardParams p) {
+    __shared__ Smem s;
+    const int b = blockIdx.x;
+    read_counters(p.counters, s);
+    const unsigned short* lr = shard_row(p.logits, p.row_stride, p.n, p.row_sel, b);
+    const float mx = bf16_bits_to_f32((unsigned short)bits_of_key16((uint32_t)p.red_max[b]));
+    derive_stats(mx, p.hist_hi + (int64_t)b * 256, p.hist_lo ? p.hist_lo + (int64_t)b * 256 : nullptr, p.top_p, false, s);
+    const RowStats st = s.st;
+    const bool draft = p.ring_out != nullptr;
+    const int j = draft ? (int)s.step : 0;
+    const bool store = draft && j >= 0 && j < p.gamma;
+    unsigned short* copy_to = store ? p.ring_out + ((int64_t)b * p.gamma + j) * p.v_loc : nullptr;
+    const NoiseKey nk = noise_key(p.seed, p.purpose, j, b, s.iter);
+    float best;
+    int bi;
+    draw_shard<NT>(lr, p.v_loc, p.vocab_offset, st, p.invT, nk, s, copy_to, best, bi);
+    if (threadIdx.x == 0) {
+        p.out[b] = pack_cand(best, bi);
+        if (store) p.ring_stats[(int64_t)b * p.gamma + j] = st;
+    }
+}
+
+// phase E of a draw: the global winner (token 0 if nothing was kept anywhere) to all n columns; advances the counters
+__global__ __launch_bounds__(256) void shard_draw_finish_kernel(const long long* __restrict__ cand, int B, int n,
+                                                                int32_t* counters, int advance, int64_t* out) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b < B) {
+        const long long c = cand[b];
+        const int64_t tok = c < 0 ? 0 : (int64_t)cand_index(c);
+        for (int k = 0; k < n; ++k) out[(int64_t)b * n + k] = tok;
+    }
+    ticket_advance(counters, advance);
+}
+
+// phase D of a verify: target stats of the request's gamma + 1 rows, the accept walk from the probes (the same jr on
+// every rank), then this shard's candidates: [b, 0] the residual draw at jr or the bonus draw, [b, 1] the fallback
+// (p~ without d) at jr, [b, 2] = jr.
+template <int NT>
+__global__ __launch_bounds__(NT) void shard_verify_kernel(const ShardParams p) {
+    __shared__ Smem s;
+    const int b = blockIdx.x, G = p.gamma;
+    read_counters(p.counters, s);
+    const uint32_t iter = s.iter;
+    const int64_t* tb = p.tokens_buffer + (int64_t)b * (G + 1);
+    for (int j = 0; j <= G; ++j) {
+        const int64_t row = (int64_t)b * (G + 1) + j;
+        const float mx = bf16_bits_to_f32((unsigned short)bits_of_key16((uint32_t)p.red_max[row]));
+        derive_stats(mx, p.hist_hi + row * 256, p.hist_lo ? p.hist_lo + row * 256 : nullptr, p.top_p, false, s);
+        if (threadIdx.x == 0) p.target_stats[row] = s.st;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int jr = G;
+        for (int j = 0; j < G; ++j) {
+            const long long probe = p.red_max[(int64_t)p.R + (int64_t)b * G + j];
+            if (!((probe >> 32) & 1)) {     // d owned by no rank: outside [0, vocab_total)
+                jr = j;
+                break;
+            }
+            const float pd = prob_of((uint32_t)(probe >> 16) & 0xffffu, p.target_stats[(int64_t)b * (G + 1) + j], p.invT);
+            const float qd = prob_of((uint32_t)probe & 0xffffu, p.ring_stats[(int64_t)b * G + j], p.invT);
+            const NoiseKey nk = noise_key(p.seed, MD_SAMPLE_ACCEPT, j, b, iter);
+            const float u = uniform_of(noise_block(nk, 0).x);
+            if (!(u * qd < pd)) {
+                jr = j;
+                break;
+            }
+        }
+        s.jr = jr;
+        s.st = p.target_stats[(int64_t)b * (G + 1) + jr];
+    }
+    __syncthreads();
+    const int jr = s.jr;
+    const RowStats ps = s.st;
+    const unsigned short* tr = p.logits + ((int64_t)b * (G + 1) + jr) * p.row_stride;
+    float best, fbest = -INFINITY;
+    int bi, fbi = -1;
+    if (jr < G) {
+        const RowStats qs = p.ring_stats[(int64_t)b * G + jr];
+        const int64_t d = tb[jr + 1];
+        const unsigned short* rr = p.ring + ((int64_t)b * G + jr) * p.ring_row_stride + p.ring_col_offset;
+        const NoiseKey nk = noise_key(p.seed, MD_SAMPLE_RESIDUAL, jr, b, iter);
+        best = -INFINITY;
+        bi = 0x7fffffff;
+        fbi = 0x7fffffff;
+        int grp = -1;
+        Word4 w{0, 0, 0, 0};
+        for (int vl = threadIdx.x; vl < p.v_loc; vl += NT) {
+            const uint32_t bits = tr[vl];
+            const int v = p.vocab_offset + vl;
+            const float r = prob_of(bits, ps, p.invT) - prob_of(rr[vl], qs, p.invT);
+            const bool res = r > 0.f;
+            const bool fb = !(v == d || key16(bits) < ps.kstar);
+            if (!res && !fb) continue;
+            if ((v >> 2) != grp) {
+                grp = v >> 2;
+                w = noise_block(nk, v);
+            }
+            const float g = gumbel_of(pick(w, v));
+            if (res) {
+                const float sc = logf(r) + g;
+                if (sc > best || (sc == best && v < bi)) {
+                    best = sc;
+                    bi = v;
+                }
+            }
+            if (fb) {
+                const float sc = (bf16_bits_to_f32(bits) - ps.m) * p.invT + g;
+                if (sc > fbest || (sc == fbest && v < fbi)) {
+                    fbest = sc;
+                    fbi = v;
+                }
+            }
+        }
+        block_argmax_sc<NT>(best, bi, s);
+        block_argmax_sc<NT>(fbest, fbi, s);
+    } else {
+        const NoiseKey nk = noise_key(p.seed, MD_SAMPLE_BONUS, G, b, iter);
+        draw_shard<NT>(tr, p.v_loc, p.vocab_offset, ps, p.invT, nk, s, nullptr, best, bi);
+    }
+    if (threadIdx.x == 0) {
+        p.out[(int64_t)b * 3] = pack_cand(best, bi);
+        p.out[(int64_t)b * 3 + 1] = pack_cand(fbest, fbi);
+        p.out[(int64_t)b * 3 + 2] = jr;
+    }
+}
+
+// phase E of a verify: the last-resort rules of spec_verify_kernel on the global candidates, target_tokens in its encoding
+__global__ __launch_bounds__(256) void shard_verify_finish_kernel(const long long* __restrict__ cand,
+                                                                  const int64_t* __restrict__ tokens_buffer, int B, int G,
+                                                                  int32_t* counters, int64_t* target_tokens) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b < B) {
+        const int64_t* tb = tokens_buffer + (int64_t)b * (G + 1);
+        const long long c0 = cand[(int64_t)b * 3], c1 = cand[(int64_t)b * 3 + 1];
+        long long jr = cand[(int64_t)b * 3 + 2];
+        jr = jr < 0 ? 0 : (jr > G ? G : jr);
+        int64_t tok;
+        if (c0 >= 0)
+            tok = cand_index(c0);
+        else if (jr == G)
+            tok = 0;
+        else if (c1 >= 0)
+            tok = cand_index(c1);
+        else
+            tok = tb[jr + 1] == 0 ? 1 : 0;
+        int64_t* tt = target_tokens + (int64_t)b * (G + 1);
+        for (int j = 0; j <= G; ++j) tt[j] = j < jr ? tb[j + 1] : (j == jr ? tok : (int64_t)-1);
+    }
+    ticket_advance(counters, MD_SAMPLE_ADVANCE_ITER);
+}
+
+// what every phase reads: this rank's columns of the rows, and which row of a request is drawn
+ShardParams shard_params(const void* logits, int64_t row_stride, int R, int n, int v_loc, const int64_t* row_sel) {
+    ShardParams p{};
+    p.logits = (const unsigned short*)logits;
+    p.row_stride = row_stride;
+    p.R = R;
+    p.n = n;
+    p.v_loc = v_loc;
+    p.row_sel = row_sel;
+    return p;
+}
+
+void shard_columns(ShardParams& p, int vocab_offset, int vocab_total) {
+    p.vocab_offset = vocab_offset;
+    p.vocab_total = vocab_total;
+}
+
+void shard_filter(ShardParams& p, float temperature, float top_p) {
+    p.invT = 1.0f / temperature;
+    p.top_p = top_p;
+}
+
+void shard_reduced(ShardParams& p, const int64_t* red_max, const int64_t* hist_hi, const int64_t* hist_lo) {
+    p.red_max = (const long long*)red_max;
+    p.hist_hi = (const long long*)hist_hi;
+    p.hist_lo = (const long long*)hist_lo;
+}
+
+// the verify's view of the draft ring: a ring shard, or this rank's columns of a full ring
+void shard_ring_view(ShardParams& p, const int64_t* tokens_buffer, const void* ring, int64_t ring_row_stride,
+                     int64_t ring_col_offset) {
+    p.tokens_buffer = tokens_buffer;
+    p.ring = (const unsigned short*)ring;
+    p.ring_row_stride = ring_row_stride;
+    p.ring_col_offset = ring_col_offset;
+}
+
+#define MD_SHARD_LAUNCH(kernel, rows, grid, p, stream, what)                                                 \
+    do {                                                                                                     \
+        if (wide(rows, (p).v_loc))                                                                           \
+            hipLaunchKernelGGL((kernel<1024>), dim3(grid), dim3(1024), 0, (hipStream_t)(stream), p);         \
+        else                                                                                                 \
+            hipLaunchKernelGGL((kernel<256>), dim3(grid), dim3(256), 0, (hipStream_t)(stream), p);           \
+        MD_CHECK_LAUNCH(what);                                                                               \
+    } while (0)
+
 }  // namespace
 
 extern "C" int md_philox4x32_10_host(const uint32_t* ctr_host, int n, uint32_t key0, uint32_t key1,
@@ -580,5 +1000,144 @@ extern "C" int md_spec_verify_sample(const void* logits, int64_t row_stride, int
     else
         hipLaunchKernelGGL((spec_verify_kernel<256>), dim3(B), dim3(256), 0, (hipStream_t)stream, p);
     MD_CHECK_LAUNCH("md_spec_verify_sample");
+    return MD_OK;
+}
+
+// ---- vocab-sharded entry points (header, K11 "sharded"): the local phases; the caller all-reduces between them
+#define MD_SHARD_CHECK_SHAPE(name)                                                                                   \
+    MD_CHECK_ARG(R > 0 && n > 0 && v_loc > 0 && row_stride >= 0, name ": bad shape rows=%d n=%d v_loc=%d", R, n, v_loc)
+#define MD_SHARD_CHECK_OFFSET(name)                                                                                  \
+    MD_CHECK_ARG(vocab_offset >= 0 && vocab_total > 0 && (int64_t)vocab_offset + v_loc <= (int64_t)vocab_total,      \
+                 name ": columns [%d, %d + %d) are not inside the vocabulary of %d", vocab_offset, vocab_offset,      \
+                 v_loc, vocab_total)
+#define MD_SHARD_CHECK_TP(name)                                                                                      \
+    MD_CHECK_ARG(temperature > 0.f && top_p > 0.f && top_p <= 1.f,                                                   \
+                 name ": need temperature > 0 and 0 < top_p <= 1 (got %g, %g)", temperature, top_p)
+
+extern "C" int md_sample_shard_max(const void* logits, int64_t row_stride, int R, int n, int v_loc,
+                                   const int64_t* row_sel, const int64_t* tokens_buffer, const void* ring,
+                                   int64_t ring_row_stride, int64_t ring_col_offset, int gamma, int vocab_offset,
+                                   int vocab_total, int64_t* red_out, md_stream_t stream) {
+    MD_CHECK_ARG(logits && red_out, "md_sample_shard_max: null pointer argument");
+    MD_SHARD_CHECK_SHAPE("md_sample_shard_max");
+    MD_SHARD_CHECK_OFFSET("md_sample_shard_max");
+    if (tokens_buffer) {
+        MD_CHECK_ARG(ring && gamma >= 1 && n == 1 && row_sel == nullptr && R % (gamma + 1) == 0,
+                     "md_sample_shard_max: the verify probe needs a ring, gamma >= 1 and rows = B (gamma + 1), n = 1");
+        MD_CHECK_ARG(ring_col_offset >= 0 && ring_row_stride >= ring_col_offset + v_loc && row_stride >= v_loc,
+                     "md_sample_shard_max: ring columns [%lld, +%d) exceed its row stride %lld",
+                     (long long)ring_col_offset, v_loc, (long long)ring_row_stride);
+    }
+    ShardParams p = shard_params(logits, row_stride, R, n, v_loc, row_sel);
+    shard_columns(p, vocab_offset, vocab_total);
+    shard_ring_view(p, tokens_buffer, ring, ring_row_stride, ring_col_offset);
+    p.gamma = gamma;
+    p.out = (long long*)red_out;
+    MD_SHARD_LAUNCH(shard_max_kernel, R, R, p, stream, "md_sample_shard_max");
+    return MD_OK;
+}
+
+extern "C" int md_sample_shard_hist(const void* logits, int64_t row_stride, int R, int n, int v_loc,
+                                    const int64_t* row_sel, float temperature, float top_p, const int64_t* red_max,
+                                    const int64_t* hist_hi, int64_t* hist_out, md_stream_t stream) {
+    MD_CHECK_ARG(logits && red_max && hist_out, "md_sample_shard_hist: null pointer argument");
+    MD_SHARD_CHECK_SHAPE("md_sample_shard_hist");
+    MD_SHARD_CHECK_TP("md_sample_shard_hist");
+    MD_CHECK_ARG(hist_hi == nullptr || top_p < 1.f, "md_sample_shard_hist: top_p = 1 has no low-byte phase");
+    ShardParams p = shard_params(logits, row_stride, R, n, v_loc, row_sel);
+    shard_filter(p, temperature, top_p);
+    shard_reduced(p, red_max, hist_hi, nullptr);
+    p.out = (long long*)hist_out;
+    MD_SHARD_LAUNCH(shard_hist_kernel, R, R, p, stream, "md_sample_shard_hist");
+    return MD_OK;
+}
+
+extern "C" int md_sample_shard_draw(const void* logits, int64_t row_stride, int B, int n, int v_loc, int vocab_offset,
+                                    int vocab_total, float temperature, float top_p, uint64_t seed, int purpose,
+                                    const int64_t* row_sel, const int32_t* counters, const int64_t* red_max,
+                                    const int64_t* hist_hi, const int64_t* hist_lo, void* ring, void* ring_stats,
+                                    int gamma, int64_t* cand_out, md_stream_t stream) {
+    const int R = B;
+    MD_CHECK_ARG(logits && counters && red_max && hist_hi && cand_out, "md_sample_shard_draw: null pointer argument");
+    MD_SHARD_CHECK_SHAPE("md_sample_shard_draw");
+    MD_SHARD_CHECK_OFFSET("md_sample_shard_draw");
+    MD_SHARD_CHECK_TP("md_sample_shard_draw");
+    MD_CHECK_ARG((hist_lo != nullptr) == (top_p < 1.f),
+                 "md_sample_shard_draw: the low-byte histogram goes with top_p < 1, and only with it");
+    MD_CHECK_ARG(purpose >= 0 && purpose <= MD_SAMPLE_BONUS, "md_sample_shard_draw: bad purpose %d", purpose);
+    MD_CHECK_ARG((ring == nullptr) == (ring_stats == nullptr), "md_sample_shard_draw: ring and ring_stats go together");
+    MD_CHECK_ARG(ring == nullptr || gamma >= 1, "md_sample_shard_draw: a draft ring needs gamma >= 1");
+    ShardParams p = shard_params(logits, row_stride, R, n, v_loc, row_sel);
+    shard_columns(p, vocab_offset, vocab_total);
+    shard_filter(p, temperature, top_p);
+    shard_reduced(p, red_max, hist_hi, hist_lo);
+    p.gamma = gamma;
+    p.purpose = purpose;
+    p.seed = seed;
+    p.ring_out = (unsigned short*)ring;
+    p.ring_stats = (RowStats*)ring_stats;
+    p.counters = const_cast<int32_t*>(counters);
+    p.out = (long long*)cand_out;
+    MD_SHARD_LAUNCH(shard_draw_kernel, B, B, p, stream, "md_sample_shard_draw");
+    return MD_OK;
+}
+
+extern "C" int md_sample_shard_finish(const int64_t* cand, int B, int n, int32_t* counters, int advance,
+                                      int64_t* tokens_out, md_stream_t stream) {
+    MD_CHECK_ARG(cand && counters && tokens_out, "md_sample_shard_finish: null pointer argument");
+    MD_CHECK_ARG(B > 0 && n > 0, "md_sample_shard_finish: bad shape B=%d n=%d", B, n);
+    MD_CHECK_ARG(advance >= MD_SAMPLE_ADVANCE_NONE && advance <= MD_SAMPLE_ADVANCE_ITER,
+                 "md_sample_shard_finish: bad advance mode %d", advance);
+    hipLaunchKernelGGL(shard_draw_finish_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                       (const long long*)cand, B, n, counters, advance, tokens_out);
+    MD_CHECK_LAUNCH("md_sample_shard_finish");
+    return MD_OK;
+}
+
+extern "C" int md_spec_verify_shard(const void* logits, int64_t row_stride, int B, int gamma, int v_loc,
+                                    int vocab_offset, int vocab_total, float temperature, float top_p, uint64_t seed,
+                                    const int64_t* tokens_buffer, const void* ring, int64_t ring_row_stride,
+                                    int64_t ring_col_offset, const void* ring_stats, const int64_t* red_max,
+                                    const int64_t* hist_hi, const int64_t* hist_lo, void* target_stats,
+                                    const int32_t* counters, int64_t* cand_out, md_stream_t stream) {
+    const int n = 1;
+    MD_CHECK_ARG(logits && tokens_buffer && ring && ring_stats && red_max && hist_hi && target_stats && counters &&
+                     cand_out,
+                 "md_spec_verify_shard: null pointer argument");
+    MD_CHECK_ARG(B > 0 && gamma >= 1 && (int64_t)B * (gamma + 1) <= 0x7fffffff,
+                 "md_spec_verify_shard: bad shape B=%d gamma=%d", B, gamma);
+    const int R = B * (gamma + 1);
+    MD_SHARD_CHECK_SHAPE("md_spec_verify_shard");
+    MD_CHECK_ARG(row_stride >= v_loc, "md_spec_verify_shard: row stride %lld below the local width %d",
+                 (long long)row_stride, v_loc);
+    MD_SHARD_CHECK_OFFSET("md_spec_verify_shard");
+    MD_SHARD_CHECK_TP("md_spec_verify_shard");
+    MD_CHECK_ARG((hist_lo != nullptr) == (top_p < 1.f),
+                 "md_spec_verify_shard: the low-byte histogram goes with top_p < 1, and only with it");
+    MD_CHECK_ARG(ring_col_offset >= 0 && ring_row_stride >= ring_col_offset + v_loc,
+                 "md_spec_verify_shard: ring columns [%lld, +%d) exceed its row stride %lld", (long long)ring_col_offset,
+                 v_loc, (long long)ring_row_stride);
+    ShardParams p = shard_params(logits, row_stride, R, n, v_loc, nullptr);
+    shard_columns(p, vocab_offset, vocab_total);
+    shard_filter(p, temperature, top_p);
+    shard_reduced(p, red_max, hist_hi, hist_lo);
+    shard_ring_view(p, tokens_buffer, ring, ring_row_stride, ring_col_offset);
+    p.gamma = gamma;
+    p.seed = seed;
+    p.ring_stats = (RowStats*)const_cast<void*>(ring_stats);
+    p.target_stats = (RowStats*)target_stats;
+    p.counters = const_cast<int32_t*>(counters);
+    p.out = (long long*)cand_out;
+    MD_SHARD_LAUNCH(shard_verify_kernel, B, B, p, stream, "md_spec_verify_shard");
+    return MD_OK;
+}
+
+extern "C" int md_spec_verify_shard_finish(const int64_t* cand, const int64_t* tokens_buffer, int B, int gamma,
+                                           int32_t* counters, int64_t* target_tokens, md_stream_t stream) {
+    MD_CHECK_ARG(cand && tokens_buffer && counters && target_tokens, "md_spec_verify_shard_finish: null pointer argument");
+    MD_CHECK_ARG(B > 0 && gamma >= 1, "md_spec_verify_shard_finish: bad shape B=%d gamma=%d", B, gamma);
+    hipLaunchKernelGGL(shard_verify_finish_kernel, dim3((B + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                       (const long long*)cand, tokens_buffer, B, gamma, counters, target_tokens);
+    MD_CHECK_LAUNCH("md_spec_verify_shard_finish");
     return MD_OK;
 }

@@ -860,6 +860,212 @@ def spec_verify_sample(logits, tokens_buffer, ring, ring_stats, target_stats, co
     return out
 
 
+# ---- the vocab-sharded phases (K11 "sharded"): local launches; the caller all-reduces red / hist / cand between them
+HIST_BINS = 256
+CAND_WORDS = 3           # md_spec_verify_shard: residual-or-bonus candidate, fallback candidate, jr
+
+
+def _shard_rows(what, logits, n, row_sel):
+    rows, v_loc = logits.shape
+    if n < 1 or rows % n:
+        raise ValueError(f"{what}: {rows} rows are not R x n = {n}")
+    R = rows // n
+    if row_sel is not None:
+        _gpu(row_sel)
+        if row_sel.dtype != torch.int64 or row_sel.numel() != R or not row_sel.is_contiguous():
+            raise ValueError(f"{what}: row_sel must be a contiguous int64 [{R}] tensor")
+    return R, v_loc
+
+
+def _shard_offset(what, v_loc, vocab_offset, vocab_total):
+    if vocab_offset < 0 or vocab_total < 1 or vocab_offset + v_loc > vocab_total:
+        raise ValueError(f"{what}: columns [{vocab_offset}, {vocab_offset} + {v_loc}) are not inside the vocabulary "
+                         f"of {vocab_total}")
+
+
+def _shard_buf(what, name, t, shape):
+    if t is None or t.dtype != torch.int64 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{what}: {name} must be a contiguous int64 {list(shape)} tensor")
+    _gpu(t)
+
+
+def _shard_ring(what, ring, B, gamma, v_loc, col_offset):
+    """The ring a verify phase reads: [B, gamma, W] bf16 with unit inner stride and dense requests (a ring shard, or a
+    column view of / an offset into a full ring) -> row stride."""
+    _gpu(ring)
+    if (ring.dim() != 3 or ring.dtype != torch.bfloat16 or ring.shape[0] != B or ring.shape[1] != gamma
+            or ring.stride(2) != 1 or ring.stride(0) != gamma * ring.stride(1)):
+        raise ValueError(f"{what}: the ring must be bf16 [B={B}, gamma={gamma}, W] with unit inner stride and "
+                         f"stride(0) = gamma * stride(1); got {tuple(ring.shape)} strides {ring.stride()}")
+    if col_offset < 0 or col_offset + v_loc > ring.shape[2]:
+        raise ValueError(f"{what}: ring columns [{col_offset}, {col_offset} + {v_loc}) exceed its width {ring.shape[2]} "
+                         "(draft and target must shard the vocabulary alike)")
+    return ring.stride(1)
+
+
+def shard_max(logits, n, vocab_offset, vocab_total, red, row_sel=None, tokens_buffer=None, ring=None,
+              ring_col_offset=0):
+    """Phase A on this rank's columns logits [R*n, v_loc] bf16: red[:R] = key of the shard's max of each drawn row.
+    With tokens_buffer [B, gamma+1] (verify; n = 1, R = B (gamma+1)) red [R + B gamma] also takes the probes of the
+    draft tokens this rank owns (0 elsewhere).  The caller MAX-all-reduces red."""
+    _gpu(logits)
+    _sample_args(logits, 1.0, 1.0)
+    R, v_loc = _shard_rows("shard_max", logits, n, row_sel)
+    _shard_offset("shard_max", v_loc, vocab_offset, vocab_total)
+    gamma, tb, stride = 0, None, 0
+    if tokens_buffer is not None:
+        if tokens_buffer.dim() != 2 or tokens_buffer.dtype != torch.int64:
+            raise ValueError("shard_max: tokens_buffer must be int64 [B, gamma+1]")
+        B, G1 = tokens_buffer.shape
+        gamma = G1 - 1
+        if n != 1 or row_sel is not None or R != B * G1 or gamma < 1 or ring is None:
+            raise ValueError(f"shard_max: a verify probe needs n = 1, no row_sel, a ring and logits of B (gamma+1) = "
+                             f"{B * G1} rows; got {R}")
+        stride = _shard_ring("shard_max", ring, B, gamma, v_loc, ring_col_offset)
+        _gpu(tokens_buffer)
+        tb = tokens_buffer.contiguous()
+    elif ring is not None:
+        raise ValueError("shard_max: a ring without tokens_buffer")
+    _shard_buf("shard_max", "red", red, (R + (R // (gamma + 1)) * gamma if gamma else R,))
+    check(_lib.load().md_sample_shard_max(_p(logits), logits.stride(0), R, n, v_loc, _p(row_sel), _p(tb), _p(ring),
+                                          stride, int(ring_col_offset), gamma, int(vocab_offset), int(vocab_total),
+                                          _p(red), _stream()), "md_sample_shard_max")
+    return red
+
+
+def shard_hist(logits, n, temperature, top_p, red, hist_out, hist_hi=None, row_sel=None):
+    """Phase B (hist_hi None) / C (hist_hi = the reduced phase-B tensor; top_p < 1): hist_out [R, 256] int64 masses of
+    this rank's columns under the global max in the reduced `red`.  The caller SUM-all-reduces hist_out."""
+    _gpu(logits)
+    _sample_args(logits, temperature, top_p)
+    R, v_loc = _shard_rows("shard_hist", logits, n, row_sel)
+    if red is None or red.dtype != torch.int64 or red.dim() != 1 or red.numel() < R or not red.is_contiguous():
+        raise ValueError(f"shard_hist: red must be a contiguous int64 tensor of at least {R} elements")
+    _gpu(red)
+    _shard_buf("shard_hist", "hist_out", hist_out, (R, HIST_BINS))
+    if hist_hi is not None:
+        if top_p >= 1:
+            raise ValueError("shard_hist: top_p = 1 has no low-byte phase")
+        _shard_buf("shard_hist", "hist_hi", hist_hi, (R, HIST_BINS))
+    check(_lib.load().md_sample_shard_hist(_p(logits), logits.stride(0), R, n, v_loc, _p(row_sel), float(temperature),
+                                           float(top_p), _p(red), _p(hist_hi), _p(hist_out), _stream()),
+          "md_sample_shard_hist")
+    return hist_out
+
+
+def _shard_hists(what, R, top_p, hist_hi, hist_lo):
+    _shard_buf(what, "hist_hi", hist_hi, (R, HIST_BINS))
+    if (hist_lo is not None) != (top_p < 1):
+        raise ValueError(f"{what}: the low-byte histogram goes with top_p < 1, and only with it")
+    if hist_lo is not None:
+        _shard_buf(what, "hist_lo", hist_lo, (R, HIST_BINS))
+
+
+def shard_draw(logits, n, vocab_offset, vocab_total, temperature, top_p, seed, purpose, counters, red, hist_hi, hist_lo,
+               cand, row_sel=None, ring=None, ring_stats=None):
+    """Phase D of a draw: cand [B] int64 = this rank's Gumbel-max winner (global index) under the stats derived from
+    the reduced red / hist_hi / hist_lo (hist_lo None iff top_p == 1).  Draft mode (ring [B, gamma, v_loc] bf16 = this
+    rank's ring shard, ring_stats [B, gamma, 2]): the local columns and the stats go to slot counters[1].  The caller
+    MAX-all-reduces cand; the counters are only read."""
+    _gpu(logits, counters)
+    _sample_args(logits, temperature, top_p)
+    B, v_loc = _shard_rows("shard_draw", logits, n, row_sel)
+    _shard_offset("shard_draw", v_loc, vocab_offset, vocab_total)
+    if (ring is None) != (ring_stats is None):
+        raise ValueError("shard_draw: ring and ring_stats go together")
+    _sample_state(counters, ring_stats=ring_stats)
+    _shard_buf("shard_draw", "red", red, (B,))
+    _shard_hists("shard_draw", B, top_p, hist_hi, hist_lo)
+    _shard_buf("shard_draw", "cand", cand, (B,))
+    gamma = 0
+    if ring is not None:
+        _gpu(ring, ring_stats)
+        if (ring.dim() != 3 or ring.shape[0] != B or ring.shape[2] != v_loc or not ring.is_contiguous()
+                or ring.dtype != torch.bfloat16):
+            raise ValueError(f"shard_draw: the ring shard must be a contiguous bf16 [B={B}, gamma, v_loc={v_loc}] tensor; "
+                             f"got {tuple(ring.shape)}")
+        gamma = ring.shape[1]
+        if gamma < 1:
+            raise ValueError("shard_draw: a draft ring needs gamma >= 1")
+        if tuple(ring_stats.shape) != (B, gamma, STATS_WORDS) or not ring_stats.is_contiguous():
+            raise ValueError("shard_draw: ring_stats must be a contiguous [B, gamma, 2] int64 tensor")
+    check(_lib.load().md_sample_shard_draw(_p(logits), logits.stride(0), B, n, v_loc, int(vocab_offset),
+                                           int(vocab_total), float(temperature), float(top_p),
+                                           int(seed) & 0xFFFFFFFFFFFFFFFF, int(purpose), _p(row_sel), _p(counters),
+                                           _p(red), _p(hist_hi), _p(hist_lo), _p(ring), _p(ring_stats), gamma, _p(cand),
+                                           _stream()), "md_sample_shard_draw")
+    return cand
+
+
+def shard_finish(cand, n, counters, advance, out=None):
+    """Phase E of a draw: the reduced cand [B] -> tokens [B, n] int64 (the token in every column); advances the counters."""
+    _gpu(cand, counters)
+    _sample_state(counters, cand=cand, out=out)
+    if cand.dim() != 1 or not cand.is_contiguous():
+        raise ValueError("shard_finish: cand must be a contiguous int64 [B] tensor")
+    B = cand.numel()
+    if out is None:
+        out = torch.empty((B, n), dtype=torch.int64, device=cand.device)
+    elif tuple(out.shape) != (B, n) or not out.is_contiguous():
+        raise ValueError(f"shard_finish: out must be a contiguous [B={B}, n={n}] tensor")
+    check(_lib.load().md_sample_shard_finish(_p(cand), B, n, _p(counters), int(advance), _p(out), _stream()),
+          "md_sample_shard_finish")
+    return out
+
+
+def spec_verify_shard(logits, tokens_buffer, vocab_offset, vocab_total, ring, ring_stats, red, hist_hi, hist_lo,
+                      target_stats, counters, temperature, top_p, seed, cand, ring_col_offset=0):
+    """Phase D of a verify on this rank's columns logits [B*(gamma+1), v_loc]: the target stats of every row (from the
+    reduced red [B (gamma+1) + B gamma] / hist_hi / hist_lo) into target_stats, the accept walk from the probes, and
+    cand [B, 3] int64 = (residual-or-bonus candidate, fallback candidate, jr).  ring: [B, gamma, W] -- this rank's ring
+    shard, or a full ring with ring_col_offset = vocab_offset.  The caller MAX-all-reduces cand."""
+    _gpu(logits, tokens_buffer, ring_stats, target_stats, counters)
+    _sample_args(logits, temperature, top_p)
+    _sample_state(counters, tokens_buffer=tokens_buffer, ring_stats=ring_stats, target_stats=target_stats)
+    if tokens_buffer.dim() != 2:
+        raise ValueError("spec_verify_shard: tokens_buffer must be [B, gamma+1]")
+    B, G1 = tokens_buffer.shape
+    rows, v_loc = logits.shape
+    if rows != B * G1 or G1 < 2:
+        raise ValueError(f"spec_verify_shard: logits {tuple(logits.shape)} and tokens_buffer "
+                         f"{tuple(tokens_buffer.shape)} disagree")
+    _shard_offset("spec_verify_shard", v_loc, vocab_offset, vocab_total)
+    stride = _shard_ring("spec_verify_shard", ring, B, G1 - 1, v_loc, ring_col_offset)
+    if (tuple(target_stats.shape) != (rows, STATS_WORDS) or tuple(ring_stats.shape) != (B, G1 - 1, STATS_WORDS)
+            or not target_stats.is_contiguous() or not ring_stats.is_contiguous()):
+        raise ValueError("spec_verify_shard: stats tensors must be contiguous [rows, 2] / [B, gamma, 2] int64")
+    _shard_buf("spec_verify_shard", "red", red, (rows + B * (G1 - 1),))
+    _shard_hists("spec_verify_shard", rows, top_p, hist_hi, hist_lo)
+    _shard_buf("spec_verify_shard", "cand", cand, (B, CAND_WORDS))
+    tb = tokens_buffer.contiguous()
+    check(_lib.load().md_spec_verify_shard(_p(logits), logits.stride(0), B, G1 - 1, v_loc, int(vocab_offset),
+                                           int(vocab_total), float(temperature), float(top_p),
+                                           int(seed) & 0xFFFFFFFFFFFFFFFF, _p(tb), _p(ring), stride,
+                                           int(ring_col_offset), _p(ring_stats), _p(red), _p(hist_hi), _p(hist_lo),
+                                           _p(target_stats), _p(counters), _p(cand), _stream()), "md_spec_verify_shard")
+    return cand
+
+
+def spec_verify_shard_finish(cand, tokens_buffer, counters, out=None):
+    """Phase E of a verify: the reduced cand [B, 3] -> target_tokens [B, gamma+1] in the encoding of spec_verify_sample;
+    advances the iteration counter."""
+    _gpu(cand, tokens_buffer, counters)
+    _sample_state(counters, cand=cand, tokens_buffer=tokens_buffer, out=out)
+    if tokens_buffer.dim() != 2 or tokens_buffer.shape[1] < 2:
+        raise ValueError("spec_verify_shard_finish: tokens_buffer must be [B, gamma+1]")
+    B, G1 = tokens_buffer.shape
+    if tuple(cand.shape) != (B, CAND_WORDS) or not cand.is_contiguous():
+        raise ValueError(f"spec_verify_shard_finish: cand must be a contiguous int64 [B={B}, 3] tensor")
+    if out is None:
+        out = torch.empty((B, G1), dtype=torch.int64, device=cand.device)
+    elif tuple(out.shape) != (B, G1) or not out.is_contiguous():
+        raise ValueError(f"spec_verify_shard_finish: out must be a contiguous [B={B}, gamma+1={G1}] tensor")
+    tb = tokens_buffer.contiguous()
+    check(_lib.load().md_spec_verify_shard_finish(_p(cand), _p(tb), B, G1 - 1, _p(counters), _p(out), _stream()),
+          "md_spec_verify_shard_finish")
+    return out
+
+
 def philox_host(counters, key0, key1):
     """Philox4x32-10 of the library (host): counters uint32-valued [n, 4] -> [n, 4] words (numpy uint32 arrays)."""
     import numpy as np
