@@ -9,6 +9,11 @@ it; one wide run: profiles/r06_fuzz_11000_cases.txt, and profiles/sampling_fuzz_
 * paged attention: request count, ragged query-row counts (0 rows included), head grouping g in {1,2,3,4,5,7,8}, D, context
   lengths from 0 to a few thousand rows, page size in {32, 64, 128}, scattered page tables, NHD / HND pages, bf16 / fp8
   pages, causal or not -- gate of test_gpu_ops.py::test_paged_attention_vs_oracle (float64 dense reference, bf16-P bound);
+* paged attention, score regimes (test_fuzz_paged_attention_score_regimes): the same shape draw with a drawn regime of
+  tests/attn_regimes.py (integer / wide / sink / ramp / offset / saturated scores instead of N(0, 1)), a drawn sm_scale in
+  {default, 0.02, 0.25, 1.0}, power-of-two per-head fp8 scales and, where the shape admits them, drawn dev knobs (waves and
+  KV-split count of the decode / verify kernel; kernel, keys per tile and waves of the prefill kernels) -- the same gate,
+  and the saturated rows equal to their winning key's V row;
 * RoPE + paged append (separate ops and the fused launch, one or two caches, both layouts): BIT-EXACT against the oracle;
 * the four GEMM families on random (M, N, K) inside their *_supported ranges, strided x, optional bias: the float64 gate of
   test_gpu_gemm.py; the residual epilogue of the tile kernel and the split combine BIT-EXACT against the unfused sequence;
@@ -30,6 +35,7 @@ import pytest
 import torch
 
 from oracle import flashinfer_ref as fr
+from tests import attn_regimes as ar
 from tests import sampling_cases as sc
 from tests.conftest import parity_report
 from tests.parity_util import check_attention, dense_attention_f64
@@ -127,6 +133,64 @@ def test_fuzz_paged_attention(ops, seed):
         check_attention(f"fuzz-{seed} {c['mode']} B{B} g{H // KH} KH{KH} D{D} page{ps} {c['layout']}"
                         f"{' fp8' if c['fp8'] else ''}{'' if c['causal'] else ' non-causal'} n={c['ns']} L={c['lens']}",
                         out[:tot], oracle, ref64, bnd)
+
+
+@pytest.mark.parametrize("seed", cases(16))
+def test_fuzz_paged_attention_score_regimes(ops, seed):
+    c = draw_attention_case(seed)
+    r = random.Random(19000 + seed)
+    D, H, KH, B, ps = c["D"], c["H"], c["KH"], c["B"], c["page_size"]
+    g_ = H // KH
+    regime = r.choice(ar.REGIMES + ["saturated", "saturated"])
+    sm_scale = r.choice(ar.SM_SCALES)
+    sm = ar.default_scale(D) if sm_scale is None else sm_scale
+    fp8 = c["fp8"] or (D == 64 and r.random() < 0.2)
+    scales = ar.pow2_scales(KH, seed) if fp8 else None
+    reqs, sat = [], []
+    for b, (n, L) in enumerate(zip(c["ns"], c["lens"])):
+        # a saturated request needs one free key per direction below the traps; shorter ones take an integer regime
+        if regime == "saturated" and n > 0 and L - n >= min(n * g_, 32) + 16:
+            reqs.append(ar.saturated_request(n, L, KH, g_, D, 500 + seed + b, sm_scale, c["causal"], ps,
+                                             scales[0] if fp8 else None))
+            sat.append(b)
+        else:
+            one = [ar.make_request("ints8" if regime == "saturated" else regime, n, L, KH, g_, D, 500 + seed + b, sm_scale,
+                                   c["causal"])]
+            reqs += ar.fit_fp8(one, scales[0]) if fp8 else one
+    pt = ar.build_paged(reqs, ps, seed, c["scatter"], scales, c["layout"])
+    tot, n_max = sum(c["ns"]), max(max(c["ns"]), 1)
+    kn = {}
+    if n_max * g_ <= 32:
+        kn = dict(waves=r.choice([0, 4, 8]), target_wgs=r.choice([0, 1, 2 * B * KH, 4 * B * KH, 4096]))
+    else:
+        kn = dict(mfma32=r.choice([-1, 0, 32, 64, 128, 129]), kt=r.choice([32, 64]), nw=r.choice([0, 4, 8]))
+    args = (pt["q"], pt["ref_cache"], pt["qo"], pt["indices"], pt["indptr"], pt["last"], H, KH, D)
+    oracle = fr.batch_prefill_paged(*args, causal=c["causal"], sm_scale=sm)
+    ref64, bnd = dense_attention_f64(*args, causal=c["causal"], sm_scale=sm)
+    lib = ops._lib.load()
+    out = torch.full((tot + 2, H, D), 7.0, dtype=BF, device=DEV)          # 2 guard rows
+    try:
+        lib.md_debug_set_attn_waves(kn.get("waves", 0))
+        lib.md_debug_set_attn_target_wgs(kn.get("target_wgs", 0))
+        lib.md_debug_set_prefill_mfma32(kn.get("mfma32", -1))
+        lib.md_debug_set_prefill_kt(kn.get("kt", 64), kn.get("nw", 0))
+        ops.paged_attention(d(pt["q"]), d(pt["dev_cache"]), d(pt["qo"]), d(pt["indices"]), d(pt["indptr"]), d(pt["last"]),
+                            n_max, pt["max_pages"], ops.AttnWorkspace(DEV), causal=c["causal"], sm_scale=sm, out=out[:tot],
+                            kv_scales=(d(scales[0]), d(scales[1])) if fp8 else None, kv_layout=c["layout"])
+        torch.cuda.synchronize()
+    finally:
+        lib.md_debug_set_attn_waves(0)
+        lib.md_debug_set_attn_target_wgs(0)
+        lib.md_debug_set_prefill_mfma32(-1)
+        lib.md_debug_set_prefill_kt(64, 0)
+    tag = (f"regime-fuzz-{seed} {regime} sm{sm:.3g} {c['mode']} B{B} g{g_} KH{KH} D{D} page{ps} {c['layout']}"
+           f"{' fp8' if fp8 else ''}{'' if c['causal'] else ' non-causal'} n={c['ns']} L={c['lens']} knobs={kn}")
+    assert (out[tot:].float() == 7.0).all(), f"wrote past the last query row ({tag})"
+    if tot:
+        check_attention(tag, out[:tot], oracle, ref64, bnd)
+    for b in sat:
+        q0, q1 = int(pt["qo"][b]), int(pt["qo"][b + 1])
+        assert ar.rows_equal(out[q0:q1], ar.saturated_expected(reqs[b], pt["v_ref"][b]), signed_zero=fp8), f"saturated rows, request {b} ({tag})"
 
 
 # ----------------------------------------------------------------------------------------- rope + append

@@ -42,6 +42,22 @@ def test_fake_kernels_and_cpu_rejection():
         torch.ops.mylib.draft_decode(torch.empty(8, 4, 64, dtype=BF), torch.empty(3, 2, 128, 2, 64, dtype=BF))
 
 
+def test_plan_forwards_sm_scale_to_paged_attention(monkeypatch):
+    """A non-default sm_scale given to plan() is what run() hands to ops.paged_attention (None = the op's 1/sqrt(D));
+    the GPU twin (tests/test_gpu_attn_regimes.py) checks that the kernel then honours it."""
+    from magicdec_amd import mylib_ops, ops
+    seen = []
+    monkeypatch.setattr(ops, "paged_attention", lambda q, kv, *a, **kw: seen.append(kw["sm_scale"]) or q)
+    ip = torch.tensor([0, 4], dtype=torch.int32)
+    q, kv = torch.zeros(4, 4, 64, dtype=BF), torch.zeros(3, 2, 128, 2, 64, dtype=BF)
+    for want in (0.25, None):
+        w = mylib_ops.PagedAttentionPlan(None, "NHD")
+        w.plan(ip, torch.tensor([0, 1], dtype=torch.int32), torch.zeros(1, dtype=torch.int32),
+               torch.ones(1, dtype=torch.int32), 4, 2, 64, 128, q_data_type=BF, causal=True, sm_scale=want)
+        assert w.run(q, kv) is q
+    assert seen == [0.25, None]
+
+
 @pytest.mark.gpu
 def test_mylib_ops_on_gpu_match_the_oracle():
     from magicdec_amd import mylib_ops
