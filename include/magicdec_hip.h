@@ -496,6 +496,33 @@ int md_accept_rollback(int64_t* tokens_buffer, const int64_t* target_tokens, int
  *   the stored md_sample_stats.m can differ; l - m, every mass and every token are the same.
  *   Status: validated bit for bit against the one-GPU entry points with the ranks emulated in one process on one GPU,
  *   and as two processes sharing one GPU over gloo (tests/test_gpu_sampling_tp.py); it has not run across physical GPUs.
+ * Per-request form (md_sample_rows_req / md_spec_verify_sample_req; one GPU only).  Request b has T[b] (fp32), top_p[b]
+ *   (fp32) and top_k[b] (int32; the pointer may be NULL: off for all), [B] each in device memory and read by the
+ *   kernels at launch time, so one captured hipGraph serves every parameter change.  Everything above -- key, w_v, the
+ *   tie rule, p~, the draw, the noise counter layout, the verify walk, the residual and its fallback, the target_tokens
+ *   encoding, the counters -- is applied with request b's own values; the seed stays one per run.
+ *   top-k      with 1 <= top_k[b] < vocab, token v survives iff #{u : key_u > key_v} < top_k[b]; a tie group that
+ *              straddles the k-th place is kept whole.  top_k[b] <= 0 or >= vocab: off.
+ *   order      top-k first, top-p over the survivors' mass: Z_k = sum of w_v over the top-k survivors; v is kept iff it
+ *              survives top-k and sum_{u: key_u > key_v} w_u <= top_p * Z_k (in double); Z_kept, p~ and the draw are
+ *              over the final kept set.  Equivalently: the filter above on the row with every top-k-dropped logit
+ *              replaced by -inf.  The select is a count select on the same two-level 256-bin radix (counts beside the
+ *              masses): max; high byte; low byte inside the top-k bin (kstar_k, Z_k); high-byte select with
+ *              thr = top_p * Z_k; low byte inside the top-p bin (one more pass over the row only when the two bins
+ *              differ).  kstar >= kstar_k; with top_p = 1 the stored kstar is kstar_k.  A row with top-k off runs
+ *              the passes of the scalar form, so with T[b] > 0 it gets bit for bit the token md_sample_rows /
+ *              md_spec_verify_sample give request b with (T[b], top_p[b]).
+ *   greedy     a T[b] that is not > 0 (0, negative, NaN) makes request b greedy: every draw is the token md_argmax
+ *              gives for the row (largest value, lowest index among equal ones), and a verify writes
+ *              target_tokens[b, j] = argmax(target row b*(gamma+1)+j) for all j = 0..gamma -- what the greedy loop
+ *              hands md_accept_rollback; the ring is not read for b.  A draft-mode draw of a greedy b still copies the
+ *              row to its ring slot; the stats it stores are {m, kstar = 0x10000, zkept = 0} (keys are 16 bits, so
+ *              this kstar marks "greedy"; p~ under it is 0 everywhere).  target_stats rows of a greedy b hold
+ *              {m, 0x10000, the row's argmax}.
+ *   invalid    device values never fault: top_p[b] outside (0, 1), NaN included, is treated as 1; top_k as above;
+ *              T as above.  No entry point reads the values on the host.
+ *   Limits: one rank only -- the sharded phases keep one (T, top_p) per run and have no top-k (a count histogram
+ *   through phases B / C and their collectives is not built); one seed per run.
  * md_philox4x32_10_host: out[i] = Philox4x32-10(ctr[i], {key0, key1}) for n counters of 4 words (host memory). Host.
  * ---------------------------------------------------------------------- */
 #define MD_SAMPLE_PREFILL 0
@@ -522,6 +549,19 @@ int md_spec_verify_sample(const void* logits, int64_t row_stride, int B, int gam
                           float top_p, uint64_t seed, const int64_t* tokens_buffer /* [B,gamma+1] */,
                           const void* ring, const void* ring_stats, void* target_stats /* [B*(gamma+1)] */,
                           int32_t* counters, int64_t* target_tokens /* [B,gamma+1] */, md_stream_t stream);
+int md_sample_rows_req(const void* logits, int64_t row_stride, int B, int n, int vocab,
+                       const float* temperature /* [B] */, const float* top_p /* [B] */,
+                       const int32_t* top_k /* [B] or NULL */, uint64_t seed, int purpose,
+                       const int64_t* row_sel /* [B] or NULL */, int32_t* counters, int advance,
+                       void* ring /* [B,gamma,vocab] bf16 or NULL */,
+                       void* ring_stats /* md_sample_stats [B,gamma] or NULL */, int gamma,
+                       int64_t* tokens_out /* [B,n] */, md_stream_t stream);
+int md_spec_verify_sample_req(const void* logits, int64_t row_stride, int B, int gamma, int vocab,
+                              const float* temperature /* [B] */, const float* top_p /* [B] */,
+                              const int32_t* top_k /* [B] or NULL */, uint64_t seed,
+                              const int64_t* tokens_buffer /* [B,gamma+1] */, const void* ring, const void* ring_stats,
+                              void* target_stats /* [B*(gamma+1)] */, int32_t* counters,
+                              int64_t* target_tokens /* [B,gamma+1] */, md_stream_t stream);
 int md_sample_shard_max(const void* logits, int64_t row_stride, int R, int n, int v_loc,
                         const int64_t* row_sel /* [R] or NULL */, const int64_t* tokens_buffer /* verify, or NULL */,
                         const void* ring, int64_t ring_row_stride, int64_t ring_col_offset, int gamma, int vocab_offset,

@@ -11,12 +11,14 @@ to the role its back-end set for the step:
 
 Everything the kernels read lives here, allocated once, before any graph capture: the iteration counter and the
 draft-step index are device tensors the kernels advance themselves, so one captured graph per step serves every
-iteration.  One temperature / top_p per run (changing them after a capture needs clear_graphs()).
+iteration.  Sampler holds one temperature / top_p per run (changing them after a capture needs clear_graphs());
+RequestSampler holds a temperature, a top_p and a top_k per request in device tensors the kernels read at launch time,
+so they change under captured graphs, and a batch may mix greedy and sampled requests.
 
-Sampler is the one-GPU form and rejects tensor-parallel models.  ShardedSampler is the opt-in form for a vocab-sharded
-lm head (Engine/tp.py:apply_tp): the same semantics and the same bits, as a chain of local launches with one small
-all-reduce between two of them (K11 "sharded": 4 collectives per call, 3 at top_p = 1).  The phases are validated with
-the ranks emulated in one process on one GPU, the class by two processes sharing one GPU over gloo
+Sampler and RequestSampler are the one-GPU forms and reject tensor-parallel models.  ShardedSampler is the opt-in form
+for a vocab-sharded lm head (Engine/tp.py:apply_tp): the same semantics and the same bits, as a chain of local launches
+with one small all-reduce between two of them (K11 "sharded": 4 collectives per call, 3 at top_p = 1).  The phases are
+validated with the ranks emulated in one process on one GPU, the class by two processes sharing one GPU over gloo
 (tests/test_gpu_sampling_tp.py); nothing here has run across physical GPUs.
 """
 from __future__ import annotations
@@ -24,7 +26,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from .. import ops
+from .. import ops, sampling_ops
 
 ROLES = ("prefill", "baseline", "draft", "verify")
 
@@ -101,6 +103,84 @@ class Sampler:
         raise ValueError(f"sampling: step role {role!r} is not one of {ROLES}")
 
 
+def _per_request(name, value, B, low_ok, what):
+    """A scalar or a length-B sequence -> list of B host values, each passing `low_ok`."""
+    vals = [value] * B if not hasattr(value, "__len__") else list(value)
+    if len(vals) != B:
+        raise ValueError(f"{name}: {len(vals)} values for {B} requests")
+    for v in vals:
+        if not low_ok(v):
+            raise ValueError(f"{name} must be {what}, got {v}")
+    return vals
+
+
+def _temperature_ok(v):
+    """0 (greedy), or a value whose fp32 form is finite and positive with a finite fp32 reciprocal: the kernels compute
+    invT = fp32(1 / T), and an infinite or zero invT turns the masses into NaN or all-equal."""
+    if not v >= 0:
+        return False
+    if v == 0:
+        return True
+    t = torch.tensor(float(v), dtype=torch.float32)
+    return bool(torch.isfinite(t) and t > 0 and torch.isfinite(1.0 / t))
+
+
+class RequestSampler(Sampler):
+    """Sampler whose temperature, top_p and top_k are per request (K11 "per request"): three [B] device tensors,
+    allocated once and read by the kernels at launch time.  set_params() copies new values in place and is allowed after
+    a capture -- the captured steps hold the tensors, not the values.  temperature 0 makes a request greedy (its tokens
+    are the argmax of its rows, its verify row what the greedy loop hands the accept kernel), so a batch may mix greedy
+    and sampled requests, and an all-greedy batch is legal; top_k 0 is off.  One seed per run.
+
+    One rank only.  The sharded phases (ShardedSampler) keep one (temperature, top_p) per run and have no top-k: that
+    needs a count histogram through phases B / C and their collectives, which is not built."""
+
+    def __init__(self, temperature, top_p, top_k, seed, B, gamma, vocab, device):
+        Sampler.__init__(self, 1.0, 1.0, seed, B, gamma, vocab, device)
+        dev = torch.device(device)
+        self.T = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.P = torch.ones(B, dtype=torch.float32, device=dev)
+        self.K = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.set_params(temperature, top_p, top_k)
+
+    def set_params(self, temperature, top_p, top_k=0):
+        """Each a scalar or a length-B sequence; validated on the host, copied in place (graph-safe)."""
+        B = self.B
+        t = _per_request("temperature", temperature, B, _temperature_ok,
+                         ">= 0 and, unless 0, finite in fp32 with a finite fp32 reciprocal")
+        p = _per_request("top_p", top_p, B, lambda v: 0 < v <= 1, "in (0, 1]")
+        k = _per_request("top_k", top_k, B, lambda v: int(v) == v and v >= 0, "an integer >= 0 (0 = off)")
+        self.temperature, self.top_p, self.top_k = [float(v) for v in t], [float(v) for v in p], [int(v) for v in k]
+        self.T.copy_(torch.tensor(self.temperature, dtype=torch.float32))
+        self.P.copy_(torch.tensor(self.top_p, dtype=torch.float32))
+        self.K.copy_(torch.tensor([min(v, 0x7FFFFFFF) for v in self.top_k], dtype=torch.int32))
+
+    def check_model(self, model):
+        if getattr(model, "process_group", None) is not None:
+            raise ValueError("per-request sampling supports TP = 1 only: the vocab-sharded phases take one "
+                             "(temperature, top_p) per run and have no top-k (no count histogram through their "
+                             "collectives)")
+        Sampler.check_model(self, model)
+
+    def head(self, logits, role, idx, B, n):
+        if B != self.B:
+            raise ValueError(f"per-request sampling: step of {B} requests, the sampler was built for {self.B}")
+        T, p, k, s = self.T, self.P, self.K, self.seed
+        if role == "verify":
+            if n != self.gamma + 1:
+                raise ValueError(f"verify step with {n} rows per request, sampler gamma = {self.gamma}")
+            return sampling_ops.spec_verify_sample_req(logits, idx, self.ring, self.ring_stats, self.target_stats,
+                                                       self.counters, T, p, k, s)
+        if role == "draft":
+            return sampling_ops.sample_rows_req(logits, n, T, p, k, s, ops.SAMPLE_DRAFT, self.counters,
+                                                ops.ADVANCE_STEP, row_sel=self.row_sel if n == 2 else None,
+                                                ring=self.ring, ring_stats=self.ring_stats)
+        if role in ("prefill", "baseline"):
+            purpose = ops.SAMPLE_PREFILL if role == "prefill" else ops.SAMPLE_BASELINE
+            return sampling_ops.sample_rows_req(logits, n, T, p, k, s, purpose, self.counters, ops.ADVANCE_ITER)
+        raise ValueError(f"sampling: step role {role!r} is not one of {ROLES}")
+
+
 def shard_offsets(widths):
     """Exclusive prefix sum of the ranks' local vocabulary widths -> (offsets, total).  The widths need not be equal:
     torch.chunk (Engine/tp.py) gives the last rank fewer columns."""
@@ -135,7 +215,10 @@ class ShardedSampler(Sampler):
     The draft of a longspec run is either sharded over the same ranks as the target (ring shard [B, gamma, v_loc]) or,
     with replicate_draft, whole on every rank (full ring [B, gamma, vocab], drawn by the one-GPU md_sample_rows, which
     is bit-identical on every rank).  A draft sharded over a sub-group of the target's ranks is NOT supported: the ranks
-    outside the sub-group have no ring to verify against (it would have to be all-gathered to them)."""
+    outside the sub-group have no ring to verify against (it would have to be all-gathered to them).
+
+    The sharded phases stay scalar-parameter: one (temperature, top_p) per run and no top-k.  Per-request values and a
+    top-k select (RequestSampler) would need a count histogram through phases B / C and their collectives; not built."""
 
     def __init__(self, temperature, top_p, seed, B, gamma, v_loc, device, group, replicate_draft=False):
         self.group = group

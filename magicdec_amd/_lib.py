@@ -12,7 +12,7 @@ from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_uint
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MAGICDEC_HIP_LIB: development only -- another build of the same sources (e.g. `make TIMING=1`'s instrumented library)
 LIB_PATH = os.environ.get("MAGICDEC_HIP_LIB") or os.path.join(_HERE, "libmagicdec_hip.so")
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 _lib = None
 _err = None
@@ -87,6 +87,8 @@ _SIGNATURES = {
     "md_philox4x32_10_host": (c_int, [P, I, c_uint32, c_uint32, P]),
     "md_sample_rows": (c_int, [P, L, I, I, I, c_float, c_float, c_uint64, I, P, P, I, P, P, I, P, P]),
     "md_spec_verify_sample": (c_int, [P, L, I, I, I, c_float, c_float, c_uint64, P, P, P, P, P, P, P]),
+    "md_sample_rows_req": (c_int, [P, L, I, I, I, P, P, P, c_uint64, I, P, P, I, P, P, I, P, P]),
+    "md_spec_verify_sample_req": (c_int, [P, L, I, I, I, P, P, P, c_uint64, P, P, P, P, P, P, P]),
     "md_sample_shard_max": (c_int, [P, L, I, I, I, P, P, P, L, L, I, I, I, P, P]),
     "md_sample_shard_hist": (c_int, [P, L, I, I, I, P, c_float, c_float, P, P, P, P]),
     "md_sample_shard_draw": (c_int, [P, L, I, I, I, I, I, c_float, c_float, c_uint64, I, P, P, P, P, P, P, P, I, P, P]),

@@ -86,13 +86,20 @@ def baseline_parser():
 
 
 def add_sampling_args(parser):
-    """--temperature / --top_p of the five entry points (not in the reference's scripts, whose flags the *_parser()
-    functions above reproduce exactly): temperature 0 (the default) is the greedy loop, unchanged; > 0 samples with the
-    tempered top-p filter and lossless speculative sampling (Engine/sampling.py), seeded by --seed."""
+    """--temperature / --top_p / --top_k / --sampling_params of the five entry points (not in the reference's scripts,
+    whose flags the *_parser() functions above reproduce exactly): temperature 0 (the default) is the greedy loop,
+    unchanged; > 0 samples with the tempered top-p filter and lossless speculative sampling (Engine/sampling.py), seeded
+    by --seed.  --top_k > 0 or --sampling_params selects the per-request sampler (Engine/sampling.RequestSampler)."""
     parser.add_argument('--temperature', type=float, default=0.0,
                         help='Sampling temperature; 0 = greedy decoding (default).  One rank, unless '
                              '--sharded_sampling is given.')
     parser.add_argument('--top_p', type=float, default=1.0, help='Top-p (nucleus) mass kept when sampling, in (0, 1].')
+    parser.add_argument('--top_k', type=int, default=0,
+                        help='Top-k filter applied before top-p when sampling; 0 = off (default).  One rank only.')
+    parser.add_argument('--sampling_params', type=Path, default=None, metavar='PATH',
+                        help='JSON list of exactly --B objects with optional keys temperature, top_p, top_k: the '
+                             'sampling parameters of each request (a missing key takes the value of the flag; '
+                             'temperature 0 = that request decodes greedily).  One rank only.')
     parser.add_argument('--sharded_sampling', action='store_true',
                         help='allow --temperature > 0 with several ranks in --rank_group: the vocab-sharded sampler '
                              '(Engine/sampling.ShardedSampler; same tokens as one GPU).  Opt-in: validated with ranks '
@@ -108,7 +115,19 @@ def parse_entry_args(parser, argv=None):
         parser.error(f"--temperature must be >= 0, got {args.temperature}")
     if not 0 < args.top_p <= 1:
         parser.error(f"--top_p must be in (0, 1], got {args.top_p}")
+    if not args.top_k >= 0:
+        parser.error(f"--top_k must be >= 0 (0 = off), got {args.top_k}")
     several = args.rank_group is not None and len(args.rank_group) > 1
+    if (args.top_k > 0 or args.sampling_params is not None) and several:
+        parser.error("--top_k / --sampling_params support one rank only (TP = 1): the vocab-sharded sampler takes one "
+                     "(temperature, top_p) per run and has no top-k (no count histogram through its collectives)")
+    args.request_params = None
+    if args.sampling_params is not None:
+        try:
+            args.request_params = load_sampling_params(args.sampling_params, args.B, args.temperature, args.top_p,
+                                                       args.top_k)
+        except (OSError, ValueError) as e:
+            parser.error(f"--sampling_params {args.sampling_params}: {e}")
     if args.temperature > 0 and several and not args.sharded_sampling:
         parser.error("--temperature > 0 supports one rank only (TP = 1): the vocab-sharded sampler needs cross-rank "
                      "max / Z / histogram reductions and is opt-in (--sharded_sampling)")
@@ -122,8 +141,42 @@ def parse_entry_args(parser, argv=None):
     return args
 
 
+def load_sampling_params(path, B, temperature, top_p, top_k):
+    """--sampling_params: a JSON list of exactly B objects with optional keys temperature / top_p / top_k (a missing key
+    takes the flag's value) -> (temperatures, top_ps, top_ks), range-checked.  ValueError names what is wrong."""
+    import json
+    with open(path) as f:
+        try:
+            rows = json.load(f)
+        except json.JSONDecodeError as e:
+            raise ValueError(f"not JSON ({e})") from None
+    if not isinstance(rows, list) or len(rows) != B:
+        raise ValueError(f"need a list of exactly B = {B} objects, got "
+                         f"{len(rows) if isinstance(rows, list) else type(rows).__name__}")
+    known = ("temperature", "top_p", "top_k")
+    out = ([], [], [])
+    for i, row in enumerate(rows):
+        if not isinstance(row, dict) or set(row) - set(known):
+            raise ValueError(f"entry {i} must be an object with keys among {list(known)}, got {row!r}")
+        t, p, k = row.get("temperature", temperature), row.get("top_p", top_p), row.get("top_k", top_k)
+        if isinstance(t, bool) or not isinstance(t, (int, float)) or not t >= 0:
+            raise ValueError(f"entry {i}: temperature must be >= 0, got {t!r}")
+        if isinstance(p, bool) or not isinstance(p, (int, float)) or not 0 < p <= 1:
+            raise ValueError(f"entry {i}: top_p must be in (0, 1], got {p!r}")
+        if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+            raise ValueError(f"entry {i}: top_k must be an integer >= 0, got {k!r}")
+        for lst, v in zip(out, (float(t), float(p), k)):
+            lst.append(v)
+    return out
+
+
 def _sampler(args, engine, gamma, device):
-    """The run's Sampler (None for greedy decoding)."""
+    """The run's Sampler (None for greedy decoding).  --top_k > 0 or --sampling_params: a RequestSampler."""
+    params = getattr(args, "request_params", None)
+    if getattr(args, "top_k", 0) > 0 or params is not None:
+        from .Engine.sampling import RequestSampler
+        t, p, k = params if params is not None else (args.temperature, args.top_p, args.top_k)
+        return RequestSampler(t, p, k, args.seed, args.B, gamma, engine.model.output.weight.shape[0], device)
     if args.temperature == 0:
         return None
     from .Engine.sampling import Sampler, ShardedSampler

@@ -13,7 +13,7 @@ void md_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-extern "C" int md_abi_version(void) { return 11; }
+extern "C" int md_abi_version(void) { return 12; }
 extern "C" const char* md_last_error_string(void) { return g_err; }
 // returns AND clears the calling thread's sticky HIP error (hipGetLastError): after a hipGraph capture was invalidated
 // the runtime keeps reporting that error at the next launch check until somebody has read it (Engine/graph.py fall-back)

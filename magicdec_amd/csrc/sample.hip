@@ -115,6 +115,28 @@ __device__ __forceinline__ void for_row(const unsigned short* __restrict__ row, 
     for (int v = start + threadIdx.x; v < vocab; v += NT) f(v, (uint32_t)row[v]);
 }
 
+// for_row that also copies the row to `copy_to` (may be null); 16-byte loads and stores when both are aligned
+template <int NT, class F>
+__device__ __forceinline__ void for_row_copy(const unsigned short* __restrict__ row, int vocab,
+                                             unsigned short* __restrict__ copy_to, F&& f) {
+    int start = 0;
+    if (((((uintptr_t)row) | (uintptr_t)copy_to) & 15) == 0) {
+        const int nvec = vocab >> 3;
+        for (int i = threadIdx.x; i < nvec; i += NT) {
+            const u32x4 raw = reinterpret_cast<const u32x4*>(row)[i];
+            if (copy_to) reinterpret_cast<u32x4*>(copy_to)[i] = raw;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) f(i * 8 + e, (raw[e >> 1] >> ((e & 1) * 16)) & 0xffffu);
+        }
+        start = nvec << 3;
+    }
+    for (int v = start + threadIdx.x; v < vocab; v += NT) {
+        const unsigned short b = row[v];
+        if (copy_to) copy_to[v] = b;
+        f(v, (uint32_t)b);
+    }
+}
+
 template <int NT>
 __device__ float block_max(float v, Smem& s) {
     v = wave_reduce_max(v);
@@ -261,6 +283,195 @@ __device__ void row_stats(const unsigned short* __restrict__ row, int vocab, flo
     __syncthreads();
 }
 
+// ---- per-request parameters (header, K11 "per request"): T, top_p and top_k are read from device memory
+constexpr uint32_t kGreedyMark = 0x10000u;  // kstar of a greedy row's stored stats: above every 16-bit key
+
+struct SmemReq {
+    Smem s;
+    unsigned long long lo[256];  // masses by the low byte inside the top-k bin
+    uint32_t cnt[256];           // token counts beside the mass histogram of the same pass
+};
+
+// out-of-range device values never fault: top_p outside (0, 1) (NaN included) is 1, top_k outside [1, vocab) is off (0)
+__device__ __forceinline__ float clean_top_p(float top_p) { return (top_p > 0.f && top_p < 1.f) ? top_p : 1.f; }
+__device__ __forceinline__ int clean_top_k(const int32_t* top_k, int b, int vocab) {
+    if (!top_k) return 0;
+    const int k = top_k[b];
+    return (k >= 1 && k < vocab) ? k : 0;
+}
+
+// wave 0: sel = min i such that base + sum_{j > i} cnt[j] < want (exists: i = 255 qualifies whenever base < want),
+// above = that count.  scan_select on counts; the k-th largest key lies in bin sel when the bins hold >= want - base.
+__device__ void count_select(const uint32_t* cnt, uint32_t base, uint32_t want, Smem& s) {
+    if (threadIdx.x < 64) {
+        const int l = threadIdx.x;
+        uint32_t h[4], own = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            h[e] = cnt[4 * l + e];
+            own += h[e];
+        }
+        uint32_t incl = own;  // sum over lanes >= l
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t t = __shfl_down(incl, o);
+            if (l + o < 64) incl += t;
+        }
+        uint32_t acc = base + (incl - own);
+        int n = 0, sel_here = -1;
+        uint32_t above_here = 0;
+#pragma unroll
+        for (int e = 3; e >= 0; --e) {
+            if (acc < want) {
+                ++n;
+                sel_here = 4 * l + e;
+                above_here = acc;
+            }
+            acc += h[e];
+        }
+        int total = n;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o);
+        const int sel = 256 - total;
+        if (total == 0 && l == 0) {     // unreachable for base < want; keeps s.sel defined
+            s.sel = 255;
+            s.above = base;
+        }
+        if (sel_here == sel) {
+            s.sel = sel;
+            s.above = above_here;
+        }
+    }
+    __syncthreads();
+}
+
+// row_stats with a top-k count select first (1 <= k < vocab): the stats of the row whose tokens below the k-th largest
+// key are -inf.  Passes: max; high-byte masses and counts; low byte inside the top-k bin (kstar_k, Z_k); then, when
+// top_p < 1, the high-byte select with thr = top_p * Z_k and the low byte inside the top-p bin -- from the masses
+// already in LDS when both bins coincide, else one more pass.  Result in q.s.st; its kstar is never below kstar_k.
+template <int NT>
+__device__ void row_stats_topk(const unsigned short* __restrict__ row, int vocab, float invT, float top_p, int k,
+                               SmemReq& q) {
+    Smem& s = q.s;
+    float mx = -INFINITY;
+    for_row<NT>(row, vocab, [&](int, uint32_t b) { mx = fmaxf(mx, bf16_bits_to_f32(b)); });
+    mx = block_max<NT>(mx, s);
+    for (int i = threadIdx.x; i < 256; i += NT) {
+        s.hist[i] = 0;
+        q.cnt[i] = 0;
+    }
+    __syncthreads();
+    for_row<NT>(row, vocab, [&](int, uint32_t b) {
+        const uint32_t hi = key16(b) >> 8;
+        atomicAdd(&q.cnt[hi], 1u);
+        const unsigned long long w = mass_fx(bf16_bits_to_f32(b), mx, invT);
+        if (w) atomicAdd(&s.hist[hi], w);
+    });
+    __syncthreads();
+    count_select(q.cnt, 0u, (uint32_t)k, s);
+    const int hbk = s.sel;
+    const uint32_t count_above = (uint32_t)s.above;
+    __syncthreads();
+    for (int i = threadIdx.x; i < 256; i += NT) {
+        q.lo[i] = 0;
+        q.cnt[i] = 0;
+    }
+    __syncthreads();
+    for_row<NT>(row, vocab, [&](int, uint32_t b) {
+        const uint32_t key = key16(b);
+        if ((int)(key >> 8) == hbk) {
+            atomicAdd(&q.cnt[key & 0xffu], 1u);
+            const unsigned long long w = mass_fx(bf16_bits_to_f32(b), mx, invT);
+            if (w) atomicAdd(&q.lo[key & 0xffu], w);
+        }
+    });
+    __syncthreads();
+    count_select(q.cnt, count_above, (uint32_t)k, s);
+    const int lbk = s.sel;
+    __syncthreads();
+    // the high-byte histogram of the masked row: nothing below bin hbk, the survivors' mass in it; Z_k by a tree
+    for (int i = threadIdx.x; i < 256; i += NT) {
+        if (i < hbk) s.hist[i] = 0;
+        if (i < lbk) q.lo[i] = 0;
+    }
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        unsigned long long in_bin = 0, z = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int i = 4 * threadIdx.x + e;
+            in_bin += q.lo[i];
+            if (i != hbk) z += s.hist[i];
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            in_bin += __shfl_xor(in_bin, o);
+            z += __shfl_xor(z, o);
+        }
+        if (threadIdx.x == 0) {
+            s.hist[hbk] = in_bin;
+            s.above = z + in_bin;
+            if (top_p >= 1.f) s.st = RowStats{mx, ((uint32_t)hbk << 8) | (uint32_t)lbk, z + in_bin};
+        }
+    }
+    __syncthreads();
+    if (top_p >= 1.f) return;
+    const unsigned long long Z = s.above;
+    const double thr = (double)top_p * (double)Z;
+    __syncthreads();
+    scan_select(s, 0ull, thr);
+    const int hb = s.sel;   // >= hbk: the bins below hold nothing and Z_k > thr
+    const unsigned long long above_hb = s.above;
+    __syncthreads();
+    if (hb == hbk) {
+        for (int i = threadIdx.x; i < 256; i += NT) s.hist[i] = q.lo[i];
+    } else {
+        for (int i = threadIdx.x; i < 256; i += NT) s.hist[i] = 0;
+        __syncthreads();
+        for_row<NT>(row, vocab, [&](int, uint32_t b) {
+            const uint32_t key = key16(b);
+            if ((int)(key >> 8) == hb) {
+                const unsigned long long w = mass_fx(bf16_bits_to_f32(b), mx, invT);
+                if (w) atomicAdd(&s.hist[key & 0xffu], w);
+            }
+        });
+    }
+    __syncthreads();
+    scan_select(s, above_hb, thr);
+    if (threadIdx.x == 0) s.st = RowStats{mx, ((uint32_t)hb << 8) | (uint32_t)s.sel, s.above + s.hist[s.sel]};
+    __syncthreads();
+}
+
+// the filter of request parameters (T > 0): row_stats itself when top-k is off.  Inlined into its kernels: as a
+// function of its own it calls row_stats and has to spill its return address, which gives the kernels a scratch segment
+template <int NT>
+__device__ __forceinline__ void row_stats_req(const unsigned short* __restrict__ row, int vocab, float invT,
+                                              float top_p, int k, SmemReq& q) {
+    if (k)
+        row_stats_topk<NT>(row, vocab, invT, top_p, k, q);
+    else
+        row_stats<NT>(row, vocab, invT, top_p, q.s);
+}
+
+// a greedy row: md_argmax's token (largest value, lowest index among equal ones, 0 if nothing compares above -inf);
+// optionally copies the row to `copy_to`
+template <int NT>
+__device__ int argmax_row(const unsigned short* __restrict__ row, int vocab, Smem& s,
+                          unsigned short* __restrict__ copy_to) {
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+    auto visit = [&](int v, uint32_t b) {
+        const float x = bf16_bits_to_f32(b);
+        if (x > best || (x == best && v < bi)) {
+            best = x;
+            bi = v;
+        }
+    };
+    for_row_copy<NT>(row, vocab, copy_to, visit);
+    const int t = block_argmax<NT>(best, bi, s);
+    return t < 0 ? 0 : t;
+}
+
 // Gumbel-max over the kept tokens of a row: argmax of (l - m) * invT + G(v); optionally copies the row to `copy_to`
 template <int NT>
 __device__ int draw_row(const unsigned short* __restrict__ row, int vocab, const RowStats& st, float invT,
@@ -281,22 +492,7 @@ __device__ int draw_row(const unsigned short* __restrict__ row, int vocab, const
             bi = v;
         }
     };
-    int start = 0;
-    if (((((uintptr_t)row) | (uintptr_t)copy_to) & 15) == 0) {
-        const int nvec = vocab >> 3;
-        for (int i = threadIdx.x; i < nvec; i += NT) {
-            const u32x4 raw = reinterpret_cast<const u32x4*>(row)[i];
-            if (copy_to) reinterpret_cast<u32x4*>(copy_to)[i] = raw;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) visit(i * 8 + e, (raw[e >> 1] >> ((e & 1) * 16)) & 0xffffu);
-        }
-        start = nvec << 3;
-    }
-    for (int v = start + threadIdx.x; v < vocab; v += NT) {
-        const unsigned short b = row[v];
-        if (copy_to) copy_to[v] = b;
-        visit(v, (uint32_t)b);
-    }
+    for_row_copy<NT>(row, vocab, copy_to, visit);
     const int t = block_argmax<NT>(best, bi, s);
     return t < 0 ? 0 : t;
 }
@@ -367,6 +563,50 @@ __global__ __launch_bounds__(NT) void sample_rows_kernel(const SampleParams p) {
     ticket_advance(p.counters, p.advance);
 }
 
+struct RequestParams {      // [B] each, device memory, read at launch time
+    const float* T;
+    const float* top_p;
+    const int32_t* top_k;   // or null: off
+};
+
+// sample_rows_kernel with request b's own (T, top_p, top_k).  A request whose T is not > 0 is greedy: its token is the
+// row's argmax; in draft mode its row still goes to the ring, with stats {m, kGreedyMark, 0} that no verify reads.
+template <int NT>
+__global__ __launch_bounds__(NT) void sample_rows_req_kernel(const SampleParams p, const RequestParams rp) {
+    __shared__ SmemReq q;
+    Smem& s = q.s;
+    const int b = blockIdx.x;
+    read_counters(p.counters, s);
+    int r = p.n - 1;
+    if (p.row_sel) {
+        const int64_t sel = p.row_sel[b] - 1;
+        r = sel < 0 ? 0 : (sel >= p.n ? p.n - 1 : (int)sel);
+    }
+    const unsigned short* row = p.logits + ((int64_t)b * p.n + r) * p.row_stride;
+    const bool draft = p.ring != nullptr;
+    const int j = draft ? (int)s.step : 0;
+    const bool store = draft && j >= 0 && j < p.gamma;
+    unsigned short* copy_to = store ? p.ring + ((int64_t)b * p.gamma + j) * p.vocab : nullptr;
+    const float T = rp.T[b];
+    RowStats st;
+    int tok;
+    if (T > 0.f) {      // uniform over the workgroup: one request each
+        const float invT = 1.0f / T;
+        row_stats_req<NT>(row, p.vocab, invT, clean_top_p(rp.top_p[b]), clean_top_k(rp.top_k, b, p.vocab), q);
+        st = s.st;
+        const NoiseKey nk = noise_key(p.seed, p.purpose, j, b, s.iter);
+        tok = draw_row<NT>(row, p.vocab, st, invT, nk, s, copy_to);
+    } else {
+        tok = argmax_row<NT>(row, p.vocab, s, copy_to);
+        st = RowStats{bf16_bits_to_f32(row[tok]), kGreedyMark, 0ull};
+    }
+    if (threadIdx.x == 0) {
+        for (int c = 0; c < p.n; ++c) p.out[(int64_t)b * p.n + c] = tok;
+        if (store) p.ring_stats[(int64_t)b * p.gamma + j] = st;
+    }
+    ticket_advance(p.counters, p.advance);
+}
+
 // stats of every target row of a verify step (one workgroup per row)
 template <int NT>
 __global__ __launch_bounds__(NT) void row_stats_kernel(const unsigned short* __restrict__ logits, int64_t row_stride,
@@ -374,6 +614,26 @@ __global__ __launch_bounds__(NT) void row_stats_kernel(const unsigned short* __r
     __shared__ Smem s;
     row_stats<NT>(logits + (int64_t)blockIdx.x * row_stride, vocab, invT, top_p, s);
     if (threadIdx.x == 0) out[blockIdx.x] = s.st;
+}
+
+// row_stats_kernel with the parameters of the row's request b = row / (gamma + 1).  A greedy request's rows get
+// {m, kGreedyMark, argmax of the row} instead: spec_verify_req_kernel copies the token out.
+template <int NT>
+__global__ __launch_bounds__(NT) void row_stats_req_kernel(const unsigned short* __restrict__ logits,
+                                                           int64_t row_stride, int vocab, int gamma,
+                                                           const RequestParams rp, RowStats* out) {
+    __shared__ SmemReq q;
+    const int b = blockIdx.x / (gamma + 1);
+    const unsigned short* row = logits + (int64_t)blockIdx.x * row_stride;
+    const float T = rp.T[b];
+    if (T > 0.f) {
+        row_stats_req<NT>(row, vocab, 1.0f / T, clean_top_p(rp.top_p[b]), clean_top_k(rp.top_k, b, vocab), q);
+        if (threadIdx.x == 0) out[blockIdx.x] = q.s.st;
+    } else {
+        const int tok = argmax_row<NT>(row, vocab, q.s, nullptr);
+        if (threadIdx.x == 0)
+            out[blockIdx.x] = RowStats{bf16_bits_to_f32(row[tok]), kGreedyMark, (unsigned long long)tok};
+    }
 }
 
 struct VerifyParams {
@@ -400,8 +660,7 @@ struct VerifyParams {
 // drawn from p~ with d excluded, for the same reason.)  So its accept count is jr + 1 -- cut at an EOT draft token
 // exactly as in the greedy loop -- and its bonus tt[an - 1] is the corrected token.
 template <int NT>
-__global__ __launch_bounds__(NT) void spec_verify_kernel(const VerifyParams p) {
-    __shared__ Smem s;
+__device__ __forceinline__ void verify_request(const VerifyParams& p, const float invT, Smem& s) {
     const int b = blockIdx.x, G = p.gamma;
     read_counters(p.counters, s);
     const uint32_t iter = s.iter;
@@ -416,8 +675,8 @@ __global__ __launch_bounds__(NT) void spec_verify_kernel(const VerifyParams p) {
                 jr = j;
                 break;
             }
-            const float pd = prob_of(trow(j)[d], p.target_stats[(int64_t)b * (G + 1) + j], p.invT);
-            const float qd = prob_of(rrow(j)[d], p.ring_stats[(int64_t)b * G + j], p.invT);
+            const float pd = prob_of(trow(j)[d], p.target_stats[(int64_t)b * (G + 1) + j], invT);
+            const float qd = prob_of(rrow(j)[d], p.ring_stats[(int64_t)b * G + j], invT);
             const NoiseKey nk = noise_key(p.seed, MD_SAMPLE_ACCEPT, j, b, iter);
             const float u = uniform_of(noise_block(nk, 0).x);
             if (!(u * qd < pd)) {
@@ -441,7 +700,7 @@ __global__ __launch_bounds__(NT) void spec_verify_kernel(const VerifyParams p) {
         int bi = 0x7fffffff, grp = -1;
         Word4 w{0, 0, 0, 0};
         for (int v = threadIdx.x; v < p.vocab; v += NT) {
-            const float r = prob_of(tr[v], ps, p.invT) - prob_of(rr[v], qs, p.invT);
+            const float r = prob_of(tr[v], ps, invT) - prob_of(rr[v], qs, invT);
             if (!(r > 0.f)) continue;
             if ((v >> 2) != grp) {
                 grp = v >> 2;
@@ -467,7 +726,7 @@ __global__ __launch_bounds__(NT) void spec_verify_kernel(const VerifyParams p) {
                     grp = v >> 2;
                     w = noise_block(nk, v);
                 }
-                const float sc = (bf16_bits_to_f32(bits) - ps.m) * p.invT + gumbel_of(pick(w, v));
+                const float sc = (bf16_bits_to_f32(bits) - ps.m) * invT + gumbel_of(pick(w, v));
                 if (sc > best || (sc == best && v < bi)) {
                     best = sc;
                     bi = v;
@@ -478,11 +737,34 @@ __global__ __launch_bounds__(NT) void spec_verify_kernel(const VerifyParams p) {
         }
     } else {
         const NoiseKey nk = noise_key(p.seed, MD_SAMPLE_BONUS, G, b, iter);
-        tok = draw_row<NT>(trow(G), p.vocab, p.target_stats[(int64_t)b * (G + 1) + G], p.invT, nk, s, nullptr);
+        tok = draw_row<NT>(trow(G), p.vocab, p.target_stats[(int64_t)b * (G + 1) + G], invT, nk, s, nullptr);
     }
     if (threadIdx.x == 0) {
         int64_t* tt = p.target_tokens + (int64_t)b * (G + 1);
         for (int j = 0; j <= G; ++j) tt[j] = j < jr ? tb[j + 1] : (j == jr ? (int64_t)tok : (int64_t)-1);
+    }
+}
+
+template <int NT>
+__global__ __launch_bounds__(NT) void spec_verify_kernel(const VerifyParams p) {
+    __shared__ Smem s;
+    verify_request<NT>(p, p.invT, s);
+    ticket_advance(p.counters, MD_SAMPLE_ADVANCE_ITER);
+}
+
+// spec_verify_kernel with request b's own T (its filter is in the stats row_stats_req_kernel wrote).  A greedy request
+// gets target_tokens[b, j] = argmax of target row j for every j, what the greedy loop hands the accept kernel; its ring
+// slots are not read.
+template <int NT>
+__global__ __launch_bounds__(NT) void spec_verify_req_kernel(const VerifyParams p, const float* __restrict__ T) {
+    __shared__ Smem s;
+    const int b = blockIdx.x, G = p.gamma;
+    const float t = T[b];
+    if (t > 0.f) {      // uniform over the workgroup
+        verify_request<NT>(p, 1.0f / t, s);
+    } else if (threadIdx.x == 0) {
+        for (int j = 0; j <= G; ++j)
+            p.target_tokens[(int64_t)b * (G + 1) + j] = (int64_t)p.target_stats[(int64_t)b * (G + 1) + j].zkept;
     }
     ticket_advance(p.counters, MD_SAMPLE_ADVANCE_ITER);
 }
@@ -1000,6 +1282,85 @@ extern "C" int md_spec_verify_sample(const void* logits, int64_t row_stride, int
     else
         hipLaunchKernelGGL((spec_verify_kernel<256>), dim3(B), dim3(256), 0, (hipStream_t)stream, p);
     MD_CHECK_LAUNCH("md_spec_verify_sample");
+    return MD_OK;
+}
+
+// ---- per-request entry points (header, K11 "per request"): T / top_p / top_k are device tensors of B values, so no
+// value is checked here; the kernels map every out-of-range value to a defined setting
+extern "C" int md_sample_rows_req(const void* logits, int64_t row_stride, int B, int n, int vocab,
+                                  const float* temperature, const float* top_p, const int32_t* top_k, uint64_t seed,
+                                  int purpose, const int64_t* row_sel, int32_t* counters, int advance, void* ring,
+                                  void* ring_stats, int gamma, int64_t* tokens_out, md_stream_t stream) {
+    MD_CHECK_ARG(logits && temperature && top_p && counters && tokens_out, "md_sample_rows_req: null pointer argument");
+    MD_CHECK_ARG(B > 0 && n > 0 && vocab > 0 && row_stride >= 0, "md_sample_rows_req: bad shape B=%d n=%d vocab=%d", B,
+                 n, vocab);
+    MD_CHECK_ARG(purpose >= 0 && purpose <= MD_SAMPLE_BONUS, "md_sample_rows_req: bad purpose %d", purpose);
+    MD_CHECK_ARG(advance >= MD_SAMPLE_ADVANCE_NONE && advance <= MD_SAMPLE_ADVANCE_ITER,
+                 "md_sample_rows_req: bad advance mode %d", advance);
+    MD_CHECK_ARG((ring == nullptr) == (ring_stats == nullptr), "md_sample_rows_req: ring and ring_stats go together");
+    MD_CHECK_ARG(ring == nullptr || gamma >= 1, "md_sample_rows_req: a draft ring needs gamma >= 1");
+    SampleParams p;
+    p.logits = (const unsigned short*)logits;
+    p.row_stride = row_stride;
+    p.n = n;
+    p.vocab = vocab;
+    p.purpose = purpose;
+    p.advance = advance;
+    p.gamma = gamma;
+    p.invT = 0.f;   // unused: the kernel reads the request's own
+    p.top_p = 0.f;
+    p.seed = seed;
+    p.row_sel = row_sel;
+    p.counters = counters;
+    p.ring = (unsigned short*)ring;
+    p.ring_stats = (RowStats*)ring_stats;
+    p.out = tokens_out;
+    const RequestParams rp{temperature, top_p, top_k};
+    if (wide(B, vocab))
+        hipLaunchKernelGGL((sample_rows_req_kernel<1024>), dim3(B), dim3(1024), 0, (hipStream_t)stream, p, rp);
+    else
+        hipLaunchKernelGGL((sample_rows_req_kernel<256>), dim3(B), dim3(256), 0, (hipStream_t)stream, p, rp);
+    MD_CHECK_LAUNCH("md_sample_rows_req");
+    return MD_OK;
+}
+
+extern "C" int md_spec_verify_sample_req(const void* logits, int64_t row_stride, int B, int gamma, int vocab,
+                                         const float* temperature, const float* top_p, const int32_t* top_k,
+                                         uint64_t seed, const int64_t* tokens_buffer, const void* ring,
+                                         const void* ring_stats, void* target_stats, int32_t* counters,
+                                         int64_t* target_tokens, md_stream_t stream) {
+    MD_CHECK_ARG(logits && temperature && top_p && tokens_buffer && ring && ring_stats && target_stats && counters &&
+                     target_tokens,
+                 "md_spec_verify_sample_req: null pointer argument");
+    MD_CHECK_ARG(B > 0 && gamma >= 1 && vocab > 0 && row_stride >= vocab && (int64_t)B * (gamma + 1) <= 0x7fffffff,
+                 "md_spec_verify_sample_req: bad shape B=%d gamma=%d vocab=%d", B, gamma, vocab);
+    const int rows = B * (gamma + 1);
+    const RequestParams rp{temperature, top_p, top_k};
+    if (wide(rows, vocab))
+        hipLaunchKernelGGL((row_stats_req_kernel<1024>), dim3(rows), dim3(1024), 0, (hipStream_t)stream,
+                           (const unsigned short*)logits, row_stride, vocab, gamma, rp, (RowStats*)target_stats);
+    else
+        hipLaunchKernelGGL((row_stats_req_kernel<256>), dim3(rows), dim3(256), 0, (hipStream_t)stream,
+                           (const unsigned short*)logits, row_stride, vocab, gamma, rp, (RowStats*)target_stats);
+    MD_CHECK_LAUNCH("md_spec_verify_sample_req(stats)");
+    VerifyParams p;
+    p.logits = (const unsigned short*)logits;
+    p.row_stride = row_stride;
+    p.gamma = gamma;
+    p.vocab = vocab;
+    p.invT = 0.f;   // unused: the kernel reads the request's own
+    p.seed = seed;
+    p.tokens_buffer = tokens_buffer;
+    p.ring = (const unsigned short*)ring;
+    p.ring_stats = (const RowStats*)ring_stats;
+    p.target_stats = (const RowStats*)target_stats;
+    p.counters = counters;
+    p.target_tokens = target_tokens;
+    if (wide(B, vocab))
+        hipLaunchKernelGGL((spec_verify_req_kernel<1024>), dim3(B), dim3(1024), 0, (hipStream_t)stream, p, temperature);
+    else
+        hipLaunchKernelGGL((spec_verify_req_kernel<256>), dim3(B), dim3(256), 0, (hipStream_t)stream, p, temperature);
+    MD_CHECK_LAUNCH("md_spec_verify_sample_req");
     return MD_OK;
 }
 

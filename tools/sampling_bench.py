@@ -3,6 +3,9 @@ V = 128 256): the only launches in which a sampled iteration differs from a gree
 
 Greedy head of one iteration:   3 x argmax over [B, V] (draft steps) + argmax over [B*(gamma+1), V] (verify).
 Sampled head of one iteration:  3 x md_sample_rows in draft mode (stats, draw, ring copy) + md_spec_verify_sample.
+Per-request head ("req_*" arms): the same launches through md_sample_rows_req / md_spec_verify_sample_req, whose
+temperature / top_p / top_k are [B] device tensors -- uniform parameters with top-k off (the passes of the scalar form
+plus the parameter loads), top-k 50 before top-p 0.9 (one more pass over the row), and a half-greedy batch.
 Both arms are captured into one hipGraph each (as the decode steps are) and replayed alternately in one process;
 the logits are realistic-scale random bf16 rows, re-used every iteration (the ring and stats are rewritten).
 Prints one JSON line per configuration: ms per iteration of each arm and the difference.
@@ -19,6 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
 from magicdec_amd import ops  # noqa: E402
+from magicdec_amd import sampling_ops  # noqa: E402
 
 
 def main():
@@ -55,7 +59,25 @@ def main():
             return ops.spec_verify_sample(tgt_logits, tb, ring, rst, tst, ctr, T, top_p, 123)
         return f
 
-    arms = {"greedy": greedy, "T0.6_p0.9": sampled(0.6, 0.9), "T0.6_p1.0": sampled(0.6, 1.0)}
+    def per_request(T, top_p, top_k):
+        Td = torch.tensor(T, dtype=torch.float32, device=dev)
+        Pd = torch.tensor(top_p, dtype=torch.float32, device=dev)
+        Kd = torch.tensor(top_k, dtype=torch.int32, device=dev)
+
+        def f():
+            for j in range(G):
+                sampling_ops.sample_rows_req(draft_logits[j], 1, Td, Pd, Kd, 123, ops.SAMPLE_DRAFT, ctr,
+                                             ops.ADVANCE_STEP, ring=ring, ring_stats=rst, out=tok)
+                tb[:, j + 1:j + 2] = tok
+            return sampling_ops.spec_verify_sample_req(tgt_logits, tb, ring, rst, tst, ctr, Td, Pd, Kd, 123)
+        return f
+
+    half = [0.0 if b % 2 else 0.6 for b in range(B)]
+    arms = {"greedy": greedy, "T0.6_p0.9": sampled(0.6, 0.9), "T0.6_p1.0": sampled(0.6, 1.0),
+            "req_uniform_T0.6_p0.9": per_request([0.6] * B, [0.9] * B, [0] * B),
+            "req_uniform_T0.6_p1.0": per_request([0.6] * B, [1.0] * B, [0] * B),
+            "req_T0.6_p0.9_k50": per_request([0.6] * B, [0.9] * B, [50] * B),
+            "req_half_greedy_T0.6_p0.9": per_request(half, [0.9] * B, [0] * B)}
     graphs = {}
     for name, fn in arms.items():
         s = torch.cuda.Stream()
